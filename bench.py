@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- UEGAN training throughput on MI355X (BASELINE.json: "train imgs/sec @512px bs=16 on 1/2/4/8 MI355X; infer ms/img").
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one full training iteration of the reference (trainer.py:77-119): G over both image sets, D over all five
 applications, VGG19 over both fidelity-loss images, rahinge + VGG-fidelity + multiscale-L1 losses, both backward sweeps, two
@@ -10,7 +10,17 @@ in HBM, random-init G/D of the reference architecture (conv_dim 32) and the seed
 weights unavailable).  Prints ONE JSON line (rank 0).
 
 Timed region: W warm-up steps, barrier + synchronize, exactly K steps with NO per-launch instrumentation, barrier +
-synchronize, max over ranks.  Everything below is measured AFTER it, on rank 0:
+synchronize, max over ranks; `ms_per_step` = its time / K, `value` = images/s over all ranks.  A plain run does nothing else: set-up,
+warm-up, the K steps, the --dump-outputs files, the line.
+
+--dump-outputs DIR: right after the timed region rank 0 writes what the last timed step computed, as float32 DIR/<name>.npy -- the
+five losses (d_loss, g_adv, g_percep, g_idt, g_loss), the enhanced images G(raw) and G(exp) (fake_exp, real_exp_idt) and the updated
+weights of G and D (g_weights, d_weights: every floating state-dict tensor flattened, in state-dict order).  An array longer than its cap
+(DUMP_CAP) is replaced by a fixed sample: the elements at seeded indices, ascending (< 64 MB in all).  The inputs, the initial weights
+and the image pool's draws are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds, AFTER the timed region (and after the dump): the same K steps without the per-step loss readback (`no_readback`), and,
+on rank 0:
   roofline     -- a second, instrumented pass (every convolution launch bracketed by HIP events on the launch stream):
                   * the dominant kernel (the MFMA implicit-GEMM instantiation with the most time): algorithmic FLOP/s vs dense
                     bf16 MFMA peak; `traffic` = HBM bytes per launch from separate rocprofv3 --pmc passes (profiles/pmc_traffic.json)
@@ -56,6 +66,11 @@ def parse():
     ap.add_argument("--precise", action="store_true", help="uegan_amd.set_precise(True): the generator's full-resolution chain on hi + lo pairs (with --dtype f16)")
     ap.add_argument("--no-fuse-epilogues", action="store_true", help="A/B: y4 * x1 and the residual + clamp as separate kernels instead of in dec4's / dec5.1's epilogue")
     ap.add_argument("--conv-dim", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's losses, enhanced images and updated weights "
+                                                                        "as float32 DIR/<name>.npy (rank 0; large arrays as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true", help="after the headline: the no-readback rerun, the instrumented roofline pass, inference timing, the "
+                                                        "fp32 / fp16 / fp16-precise legs, the CPU baseline and the recorded profiles (the --no-* options "
+                                                        "below drop single parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=2)
     ap.add_argument("--no-profile", action="store_true", help="skip the instrumented pass (no roofline object)")
@@ -74,7 +89,10 @@ def parse():
                                                                        "line carries comm.exposed_over_budget and a warning goes to stderr")
     ap.add_argument("--strict-comm", action="store_true", help="N > 1: exit with code 3 (after printing the line) when the exposed all-reduce time is over the budget")
     ap.set_defaults(infer=True, fp32=True)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _cpu_model():
@@ -177,6 +195,30 @@ def roofline_from_profile(rows, args, ms_per_step, world):
     return roof
 
 
+# --dump-outputs: elements kept per array (float32): 2 x 4 MB of images, up to 2 x 21 MB of weights (G: 4.16 M, D: 4.65 M at conv_dim 32)
+DUMP_CAP = {"image": 1 << 20, "weights": 5 << 20}
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, T):
+    """the last timed step's results as a caller of Trainer.train_step receives them (see the module docstring)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+
+    def flat_state(m):
+        return torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values() if t.is_floating_point()])
+
+    arrays = [(k, T.losses[k].reshape(1), None) for k in T.LOSS_KEYS]
+    arrays += [("fake_exp", T.fake_exp, "image"), ("real_exp_idt", T.real_exp_idt, "image"),
+               ("g_weights", flat_state(T.G), "weights"), ("d_weights", flat_state(T.D), "weights")]
+    for name, t, kind in arrays:
+        t = t.detach().reshape(-1)
+        if kind is not None and t.numel() > DUMP_CAP[kind]:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_CAP[kind]].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     args.prof_steps = 2
@@ -245,13 +287,17 @@ def main():
     dt = time.perf_counter() - t0
     abi_calls_per_step = (_lib.n_calls - calls0) / float(args.steps)
     host_issue_ms = host_issue / args.steps * 1e3
-    # the same K steps WITHOUT the per-step readback (the host free to run ahead; what rounds 1-4 reported as `value`), rank-local, after the timed region
-    t1 = time.perf_counter()
-    for i in range(0 if args.no_free_run else args.steps):
-        T.train_step(raws[i % nb], exps[i % nb])
-    T.sync()
-    sync()
-    dt_free = (time.perf_counter() - t1) if not args.no_free_run else dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, T)
+    # --full: the same K steps WITHOUT the per-step readback (the host free to run ahead; what rounds 1-4 reported as `value`), rank-local, after the timed region
+    dt_free = dt
+    if args.full and not args.no_free_run:
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            T.train_step(raws[i % nb], exps[i % nb])
+        T.sync()
+        sync()
+        dt_free = time.perf_counter() - t1
     comm = None
     if world > 1:
         comm = {"g_allreduce_exposed_ms_per_step": round(T.g_bucket.exposed_wait_ms() / args.steps, 4),
@@ -266,7 +312,7 @@ def main():
         # node says by itself whether the ring went over xGMI
         comm["rccl"] = {"ranks": dist.get_world_size(), "backend": dist.get_backend(), "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
                         "devices": torch.cuda.device_count()}
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 import subprocess
                 topo = subprocess.run(["rocm-smi", "--showtopotype"], capture_output=True, text=True, timeout=20).stdout
@@ -289,7 +335,7 @@ def main():
 
     # ---- instrumented pass (every rank runs it so that the collectives stay matched; only rank 0 reports)
     rows = []
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         # (one stream for this pass: with the VGG passes beside the discriminator update -- Trainer.overlap, the timed region's setting --
         # an event pair around a launch would also time the other stream's kernels sharing the chip)
         overlap_was, T.overlap = T.overlap, False
@@ -305,7 +351,7 @@ def main():
         T.overlap = overlap_was
 
     infer = None
-    if args.infer and rank == 0:
+    if args.full and args.infer and rank == 0:
         from uegan_amd import tester
         x1 = raws[0][:1].contiguous()
         for _ in range(3):
@@ -349,7 +395,7 @@ def main():
 
     # ---- the parity mode (fp32 storage: the mode that meets north_star's 1e-3 gate against the reference fixtures), timed the same way
     fp32 = fp16 = fp16p = None
-    if world == 1 and args.fp32 and args.dtype == "bf16":
+    if args.full and world == 1 and args.fp32 and args.dtype == "bf16":
         del T
         uegan_amd.set_compute_dtype(torch.float32)
         torch.manual_seed(1990)
@@ -450,14 +496,15 @@ def main():
             "losses_last_step": {k: round(v, 6) for k, v in items.items()},
             **({"tune": args.tune} if args.tune else {}),
             "loss_readback": "one 5-float device-to-host copy per step inside the timed loop (Trainer.loss_items)",
-            "no_readback": {"ms_per_step": round(dt_free / args.steps * 1e3, 3), "value": round(world * B * args.steps / dt_free, 3),
-                            "note": "the same K steps with the host free to run ahead (no per-step loss readback; rank 0's clock)"},
             "host": {"issue_ms_per_step": round(host_issue_ms, 3), "abi_calls_per_step": round(abi_calls_per_step, 1),
                      "per_rank": host_per_rank,
                      "note": "rank 0: wall time inside train_step() (Python + ctypes launch path; the device runs behind it) and C-ABI calls per "
                              "step (one call = one to four kernel launches)"},
         }
-        if not args.no_profile:
+        if args.full:
+            out["no_readback"] = {"ms_per_step": round(dt_free / args.steps * 1e3, 3), "value": round(world * B * args.steps / dt_free, 3),
+                                  "note": "the same K steps with the host free to run ahead (no per-step loss readback; rank 0's clock)"}
+        if args.full and not args.no_profile:
             out["roofline"] = roofline_from_profile(rows, args, ms_per_step, world)
             st = (_profile_json("pmc_traffic.json") or {}).get("step")
             if st and args.dtype == "bf16" and (B, S) == (16, 512):
@@ -469,7 +516,7 @@ def main():
             out["comm"] = comm
         gaps_name = "r06_step_gaps.json" if _profile_json("r06_step_gaps.json") else "r05_step_gaps.json"
         gaps = _profile_json(gaps_name) or _profile_json("r04_step_gaps.json")
-        if gaps and not args.no_profile and args.dtype == "bf16" and (B, S) == (16, 512):
+        if gaps and args.full and not args.no_profile and args.dtype == "bf16" and (B, S) == (16, 512):
             # GPU idle time of the step (rocprofv3 kernel trace of this command, tools/gpu_gaps.sh): wall - union of kernel intervals
             m = gaps["mean"]
             out["roofline"]["step"]["gpu_idle"] = {"idle_ms_per_step": m["idle_ms"], "busy_ms_per_step": m["busy_ms"], "wall_ms_per_step": m["wall_ms"],
@@ -484,11 +531,11 @@ def main():
             out["fp16_precise"] = fp16p
         dev_rec = (_profile_json("r06_bf16_deviation.json") or _profile_json("r05_bf16_deviation.json") or _profile_json("r04_bf16_deviation.json") or _profile_json("r03_bf16_deviation.json")
                    or _profile_json("r02_bf16_deviation.json"))
-        if dev_rec and args.dtype == "bf16":
+        if dev_rec and args.full and args.dtype == "bf16":
             out["bf16_deviation"] = {"source": "tests/test_parity_full.py on an MI355X (profiles/*_bf16_deviation.json): bf16 storage against the fp32 "
                                                "path / the fp32 reference fixtures", "records": dev_rec}
         vo = (dev_rec or {}).get("full_step_16x512_vs_oracle")
-        if vo and args.dtype == "bf16":
+        if vo and args.full and args.dtype == "bf16":
             # which legs of this line are inside north_star's tolerance (1e-3 relative: the five losses; the enhanced pixels) -- one full 16 x 512^2 step
             # of each storage mode against the CPU ORACLE (tests/test_oracle_at_size.py::test_train_step_full_size_16x512_against_oracle)
             def leg(m):
@@ -512,7 +559,7 @@ def main():
         if infer is not None:
             out["infer_ms_per_img"] = infer["ms_per_img"]
             out["infer"] = infer
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
         if comm is not None and comm["exposed_over_budget"]:

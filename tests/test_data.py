@@ -1,5 +1,7 @@
 """Input pipeline on the device (data_loader.py:74-82, 95-100, 113-133): uegan_input_transform against Pillow
 itself (the reference's resampler: bit-exact), and DeviceLoader against the per-image oracle with the documented draw order."""
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
@@ -86,18 +88,23 @@ def _make_tree(root, n, sizes):
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
-def test_device_loader_train_and_test(backend, tmp_path):
+def test_device_loader_train_and_test(backend, tmp_path, monkeypatch):
     use_backend(backend)
-    arrs = _make_tree(tmp_path, 7, [(40, 52), (36, 36), (61, 33)])
-    ds = data.ReferenceDataset(str(tmp_path))
+    # the sample name is the path up to its FIRST '.' (the reference's rule), so a dot anywhere in the temporary directory's absolute
+    # path would cut it short: the tree is addressed by a relative, dot-free root below the working directory
+    monkeypatch.chdir(tmp_path)
+    root = Path("data")
+    root.mkdir()
+    arrs = _make_tree(root, 7, [(40, 52), (36, 36), (61, 33)])
+    ds = data.ReferenceDataset(str(root))
     assert len(ds) == 7
-    files = sorted(p.name for p in (tmp_path / "exp").iterdir())
+    files = sorted(p.name for p in (root / "exp").iterdir())
     # listing order is rglob order (unsorted, like the reference's ReferenceDataset); map sample -> array by file name
     def arr_of(path):
         return arrs[(path.parent.name, int(path.stem[2:]))]
     assert sorted(ds[i][0].name for i in range(7)) == files
 
-    loader = data.get_train_loader(str(tmp_path), img_size=32, resize_size=16, batch_size=3, shuffle=True, num_workers=3,
+    loader = data.get_train_loader(str(root), img_size=32, resize_size=16, batch_size=3, shuffle=True, num_workers=3,
                                    generator=torch.Generator().manual_seed(11))
     assert len(loader) == 2                                            # drop_last
     g = torch.Generator().manual_seed(11)
@@ -118,7 +125,7 @@ def test_device_loader_train_and_test(backend, tmp_path):
     seen = [next(fetch) for _ in range(5)]
     assert all(s.img_exp.shape == (3, 3, 16, 16) for s in seen)
 
-    test_loader = data.get_test_loader(str(tmp_path), img_size=24, batch_size=4, num_workers=2)
+    test_loader = data.get_test_loader(str(root), img_size=24, batch_size=4, num_workers=2)
     batches = list(test_loader)
     assert [b.img_exp.shape[0] for b in batches] == [4, 3]             # no drop_last, listing order
     k = 0
@@ -130,7 +137,7 @@ def test_device_loader_train_and_test(backend, tmp_path):
             assert torch.equal(batch.img_raw[j].cpu(), O.test_transform(arr_of(b), 24))
             k += 1
     # decode in spawned processes (shared-memory segments): the same tensors as the thread workers
-    lp = data.get_train_loader(str(tmp_path), img_size=32, resize_size=16, batch_size=3, shuffle=True, num_workers=2,
+    lp = data.get_train_loader(str(root), img_size=32, resize_size=16, batch_size=3, shuffle=True, num_workers=2,
                                generator=torch.Generator().manual_seed(11), workers="process")
     got_p = list(lp)
     lp.close()
@@ -140,7 +147,7 @@ def test_device_loader_train_and_test(backend, tmp_path):
     # two ranks sharing one permutation see equally long shards of it (7 images: padded by wrap-around to 8, like DistributedSampler)
     seen = []
     for rank in range(2):
-        ld = data.get_train_loader(str(tmp_path), img_size=32, resize_size=16, batch_size=1, num_workers=1, drop_last=False,
+        ld = data.get_train_loader(str(root), img_size=32, resize_size=16, batch_size=1, num_workers=1, drop_last=False,
                                    generator=torch.Generator().manual_seed(100 + rank), shard=(rank, 2), shard_seed=3)
         seen.append([[b.img_name[0] for b in ld] for _ in range(2)])          # two epochs
         assert len(ld) == len(seen[-1][0])
@@ -151,9 +158,9 @@ def test_device_loader_train_and_test(backend, tmp_path):
         assert len(seen[0][e]) == len(seen[1][e]) == 4
     # every rank has the same number of batches whatever drop_last (a per-batch all-reduce loop cannot deadlock), and set_epoch
     # re-synchronises the permutation seed
-    lens = [len(data.get_train_loader(str(tmp_path), img_size=32, resize_size=16, batch_size=3, num_workers=1, drop_last=True, shard=(r, 2))) for r in range(2)]
+    lens = [len(data.get_train_loader(str(root), img_size=32, resize_size=16, batch_size=3, num_workers=1, drop_last=True, shard=(r, 2))) for r in range(2)]
     assert lens[0] == lens[1] == 1
-    ld = data.get_train_loader(str(tmp_path), img_size=32, resize_size=16, batch_size=1, num_workers=1, drop_last=False,
+    ld = data.get_train_loader(str(root), img_size=32, resize_size=16, batch_size=1, num_workers=1, drop_last=False,
                                generator=torch.Generator().manual_seed(100), shard=(0, 2), shard_seed=3)
     ld.set_epoch(1)
     assert [b.img_name[0] for b in ld] == seen[0][1]
@@ -166,13 +173,13 @@ def test_device_loader_train_and_test(backend, tmp_path):
     ops.set_compute_dtype(torch.float32)
     torch.manual_seed(0)
     G = models.Generator(8, "none", "LeakyReLU", False).to(batches[0].img_exp.device)
-    res = tester.run_test(G, data.get_test_loader(str(tmp_path), img_size=32, batch_size=4, num_workers=2), save_dir=str(tmp_path / "out"), tag="1.00")
+    res = tester.run_test(G, data.get_test_loader(str(root), img_size=32, batch_size=4, num_workers=2), save_dir=str(root / "out"), tag="1.00")
     assert len(res["names"]) == 7 and len(res["psnr"]) == 7 and abs(res["mean_psnr"] - sum(res["psnr"]) / 7) < 1e-12
     a0, b0, n0 = ds[0]
     want = O.to_uint8_image(tester.enhance(G, O.test_transform(arr_of(b0), 32)[None].to(batches[0].img_exp.device)).cpu())[0].numpy()
-    got_png = np.asarray(Image.open(tmp_path / "out" / ("%s_1.00_testFakeExp.png" % n0)))
+    got_png = np.asarray(Image.open(root / "out" / ("%s_1.00_testFakeExp.png" % n0)))
     assert np.array_equal(got_png, want)
     assert abs(res["psnr"][0] - O.psnr_u8(want, O.to_uint8_image(O.test_transform(arr_of(a0), 32)[None])[0].numpy())) < 1e-9
     # a crop larger than an image is the reference's error
     with pytest.raises(ValueError):
-        list(data.get_train_loader(str(tmp_path), img_size=50, resize_size=16, batch_size=2, num_workers=1))
+        list(data.get_train_loader(str(root), img_size=50, resize_size=16, batch_size=2, num_workers=1))

@@ -2,7 +2,7 @@
 # usage: tools/collect_profiles.sh <gpurun tag> <round prefix>: copy a tools/gpu_record.sh record from gpurun_out/ (scratch) into profiles/ (tracked)
 TAG=${1:-r06_final}; R=${2:-r06}
 P=profiles; G=gpurun_out
-for n in default f32 1024_b8 per_line; do tail -1 $G/bench_${TAG}_$n.log > $P/${R}_final_bench_$n.json; done
+for n in default f32 1024_b8 per_line; do tail -1 "${RESULTS_DIR:-results}/bench_${TAG}_$n.log" > $P/${R}_final_bench_$n.json; done      # (tools/gpu_final.sh's bench lines)
 cp $G/bench_conv_$TAG.log $P/${R}_final_bench_conv.log
 cp $G/bench_d_$TAG.log $P/${R}_final_bench_d.log
 cp $G/kernel_stats_$TAG.txt $P/${R}_final_kernel_stats.txt

@@ -9,6 +9,6 @@ fi
 for rep in 1 2; do
   for F in "$FA" "$FB"; do
     echo "== [$rep] flags: $F"
-    timeout 600 python bench.py $F --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'], 'img/s', d['value'])"
+    timeout 600 python bench.py --full $F --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'], 'img/s', d['value'])"
   done
 done

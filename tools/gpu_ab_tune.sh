@@ -10,5 +10,5 @@ for T in "$TA" "$TB"; do
   echo "== tune $T"
   timeout 600 python tools/bench_conv.py --batch 16 --iters 10 --filter "$FILT" --tune "$T" 2>/dev/null | grep -v "^layer" | cut -c1-110
   timeout 600 python tools/bench_conv.py --batch 32 --iters 10 --filter "$FILT" --tune "$T" 2>/dev/null | grep -v "^layer" | cut -c1-110
-  timeout 600 python bench.py --tune "$T" --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'], 'host', d['host'])"
+  timeout 600 python bench.py --full --tune "$T" --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'], 'host', d['host'])"
 done

@@ -9,4 +9,4 @@ fi
 timeout 600 python tools/bench_conv.py --batch 16 --iters 10 --filter "$FILT" 2>/dev/null | grep -v "^layer" | cut -c1-110
 timeout 600 python tools/bench_conv.py --batch 32 --iters 10 --filter "$FILT" 2>/dev/null | grep -v "^layer" | cut -c1-110
 timeout 300 python tools/bench_d.py 2>/dev/null | tail -2
-timeout 600 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'])"
+timeout 600 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-infer --no-fp32 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('step ms', d['ms_per_step'], 'no_readback', d['no_readback']['ms_per_step'])"

@@ -2,12 +2,13 @@
 # usage: tools/gpu_r6.sh <tag> [pytest -k expr]: selected GPU tests, the bench line with the fp32 / fp16 / fp16-precise legs, one-stream kernel statistics
 TAG=${1:-r6}; K=${2:-}
 mkdir -p gpurun_out; export TMPDIR=/tmp
+RES=${RESULTS_DIR:-results}; mkdir -p "$RES"      # the bench lines (full: roofline, inference, fp32 / fp16 legs, CPU baseline)
 if [ -n "$K" ]; then
   timeout 2400 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider -x -k "$K" > gpurun_out/pytest_$TAG.log 2>&1; echo "pytest rc=$?" >> gpurun_out/pytest_$TAG.log
   tail -25 gpurun_out/pytest_$TAG.log | cut -c1-400
 fi
-timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/bench_$TAG.log 2>&1
-tail -1 gpurun_out/bench_$TAG.log | python -c "
+timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$RES/bench_$TAG.log" 2>&1
+tail -1 "$RES/bench_$TAG.log" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('bf16', d['value'], d['ms_per_step'], 'free', d['no_readback']['ms_per_step'], 'host', d['host']['issue_ms_per_step'], d['host']['abi_calls_per_step'])
