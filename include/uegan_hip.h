@@ -65,7 +65,8 @@ enum {
   UEGAN_TUNE_HEADS_MFMA = 9,    /* default 1: uegan_conv2d_dgrad_padded takes the one-channel prediction heads (head_dgrad_mfma_kernel); 0: it declines them (the caller's uegan_conv2d_dgrad_ws then runs the vector-ALU kernel of round 3) */
   UEGAN_TUNE_FWD_STATS = 10,    /* default 1: uegan_conv2d_fwd_stats lets the streaming kernel emit the per-channel moments; 0: it declines (plain forward, the caller's moments pass) */
   UEGAN_TUNE_WGRAD_XCD = 11,    /* default 1: wgrad_tr_kernel orders its blocks so that all blocks of one pixel split run behind one XCD's L2 (needs a split count that is a multiple of 8); 0: launch order */
-  UEGAN_TUNE_COUNT = 12
+  UEGAN_TUNE_VGG_EPI = 12,      /* default 1: uegan_conv2d_dgrad_act_tap / uegan_conv2d_dgrad_unpool fold the fidelity-loss tap gradient / the max-pool backward into the data gradient's epilogue where conv_tall_kernel takes the layer; 0: they decline (the caller's two passes) */
+  UEGAN_TUNE_COUNT = 13
 };
 int uegan_set_tuning(int knob, int value, int* previous);
 /* on-device check of the MFMA fragment layouts this library assumes (A=I, asymmetric B). 0 = ok. */
@@ -257,6 +258,20 @@ size_t uegan_conv2d_dgrad_padded_bytes(const uegan_conv_desc* d);
  * max-pool and fidelity-loss gradients have the same `_act` form below.  C2 must be 0; workspace as for _dgrad_ws. */
 int uegan_conv2d_dgrad_act(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx1,
                            void* workspace, size_t workspace_bytes, int in_act, const void* x_act, uegan_stream_t stream);
+/* The fidelity loss's backward (uegan_amd/fused.py) with the elementwise pass behind a data gradient folded into its epilogue.  Only where the
+ * unfused route runs the same kernel (the 16-bit formats' conv_tall_kernel: same accumulation, bit-identical results) and UEGAN_TUNE_VGG_EPI is
+ * on; *applied = 1 then, else *applied = 0, nothing is launched, nothing is written, and the caller runs the two passes.
+ *  _act_tap: uegan_conv2d_dgrad_act (in_act = ReLU, x_act = a fidelity-loss tap x of the first d->B images) followed by
+ *            uegan_percep_tap_bwd_acc(act = ReLU, x, y, weight, gscale, dx1, tmp, d->B, d->H * d->W, d->C1, accumulate = 1): y = the reference
+ *            tap, tmp = the tap's scratch from uegan_percep_tap_fwd(_given).
+ *  _unpool:  uegan_conv2d_dgrad (gradient of a 2x2 max-pool's output, [B][H][W][C1]) followed by uegan_maxpool2x2_bwd_idx(in_act, y_pool, idx, ...,
+ *            dx_full, B, 2 H, 2 W, C1): y_pool = the pool's output (this conv's input), idx = its window positions (uegan_conv2d_fwd_pool_idx);
+ *            dx_full = [B][2 H][2 W][C1].  in_act must be ReLU. */
+int uegan_conv2d_dgrad_act_tap(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx1, int in_act,
+                               const void* x_act, const void* y, float weight, const float* gscale, const float* tmp, int* applied,
+                               uegan_stream_t stream);
+int uegan_conv2d_dgrad_unpool(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx_full, int in_act,
+                              const void* y_pool, const void* idx, int* applied, uegan_stream_t stream);
 size_t uegan_conv2d_wgrad_workspace_bytes(const uegan_conv_desc* d);
 /* dw_oihw (fp32, OIHW) = scale * sum_pixels pad(x) (x) dz ; dbias (fp32[Cout], may be NULL) = sum_pixels dz.
  * Both are OVERWRITTEN. */

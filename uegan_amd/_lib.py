@@ -84,6 +84,8 @@ SIGNATURES = {
     "uegan_conv2d_dgrad_workspace_bytes": (c_sz, [C.POINTER(ConvDesc)]),
     "uegan_conv2d_dgrad_ws": (c_int, [C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "uegan_conv2d_dgrad_act": (c_int, [C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_int, c_vp, c_vp]),
+    "uegan_conv2d_dgrad_act_tap": (c_int, [C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_f32, c_vp, c_vp, C.POINTER(c_int), c_vp]),
+    "uegan_conv2d_dgrad_unpool": (c_int, [C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, C.POINTER(c_int), c_vp]),
     "uegan_conv2d_fwd_stats_workspace_bytes": (c_sz, [C.POINTER(ConvDesc)]),
     "uegan_conv2d_fwd_stats": (c_int, [C.POINTER(ConvDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_sz, C.POINTER(c_int), c_vp]),
     "uegan_instnorm_apply": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

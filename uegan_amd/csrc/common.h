@@ -202,6 +202,26 @@ __device__ __forceinline__ float act_grad_of_pre(float v, int act) {
   }
 }
 
+// Gradient of one fidelity-loss tap, weight * MSE(IN(x), IN(y)), w.r.t. x (norm_loss.hip percep_grad_kernel).  conv_tall_kernel's tap epilogue
+// (conv_wide.hip) adds the same term to a data gradient and must agree with the stand-alone pass to the bit, so both evaluate it here: one
+// formula, one FMA contraction.  g = dL/dxh = k*(xh-yh), k = 2*weight*gscale/nel;  dx = rx*(g - mean(g) - xh*mean(g*xh)).
+__device__ __forceinline__ void percep_scalars(float weight, const float* gscale, int B, int HW, int C, float& k, float& inv_n) {
+  const float nel = (float)B * (float)HW * (float)C;
+  k = 2.f * weight * (gscale ? *gscale : 1.f) / nel;
+  inv_n = 1.f / (float)HW;
+}
+// per-(image, channel) constants: st = [mean_x | rstd_x | mean_y | rstd_y] (each bc = B*C), tot = [B*C][3] sums {(xh-yh)^2, xh-yh, (xh-yh)*xh}
+__device__ __forceinline__ void percep_consts(const float* st, const float* tot, size_t bc, size_t o, float k, float inv_n, float& mx, float& rx,
+                                              float& my, float& ry, float& mg, float& mgx) {
+  mx = st[o]; rx = st[bc + o]; my = st[2 * bc + o]; ry = st[3 * bc + o];
+  mg = k * tot[o * 3 + 1] * inv_n;
+  mgx = k * tot[o * 3 + 2] * inv_n;
+}
+__device__ __forceinline__ float percep_tap_grad(float x, float y, float mx, float rx, float my, float ry, float k, float mg, float mgx) {
+  const float xh = (x - mx) * rx, yh = (y - my) * ry;
+  return rx * (k * (xh - yh) - mg - xh * mgx);
+}
+
 // reflection index: valid for -n < i < 2n-1 (single reflection, pad < n as nn.ReflectionPad2d requires)
 __host__ __device__ __forceinline__ int reflect_idx(int i, int n) {
   i = i < 0 ? -i : i;

@@ -17,7 +17,7 @@ namespace uegan {
 
 static int g_conv_impl = UEGAN_IMPL_AUTO;
 // launch-variant thresholds (uegan_set_tuning): process-wide, set explicitly through the C ABI -- the library never reads the environment
-int g_tuning[UEGAN_TUNE_COUNT] = {256, -1, 0, 192, 192, 0, 1, 1, 1, 1, 1, 1};
+int g_tuning[UEGAN_TUNE_COUNT] = {256, -1, 0, 192, 192, 0, 1, 1, 1, 1, 1, 1, 1};
 int g_abl_stream = 0, g_abl_wide = 0;
 #ifdef UEGAN_TOOLS_BUILD
 extern "C" int uegan_tools_set_ablation(int stream_wgrad_bits, int wide_variant) {
@@ -1917,6 +1917,68 @@ extern "C" int uegan_conv2d_dgrad_act(const uegan_conv_desc* d, const void* dz, 
   }
   if (rc || applied) return rc;
   return uegan_act_bwd(d->dtype, in_act, dx1, x_act, dx1, (int64_t)d->B * d->H * d->W * d->C1, stream);
+}
+
+// ---- the fidelity loss's backward: a data gradient with the next elementwise pass in conv_tall_kernel's epilogue (ConvArgs::epi)
+// Only where the unfused route hands the SAME problem to conv_tall_kernel (run_gather_gemm -> dispatch_conv_gemm, the checks in their order):
+// the accumulation is then the same and the fused result is bit-identical to the two passes.  The arguments as uegan_conv2d_dgrad_act builds them.
+static void dgrad_epi_args(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* out, ConvArgs& a) {
+  ConvGeom& g = a.g;
+  g.B = d->B; g.IH = d->Ho; g.IW = d->Wo; g.C1 = d->Cout; g.C2 = 0; g.C = d->Cout;
+  g.OH = d->H; g.OW = d->W; g.KH = d->KH; g.KW = d->KW; g.stride = d->stride; g.pad = d->pad; g.pad_mode = d->pad_mode;
+  g.mode = 1;
+  a.in1 = dz; a.in2 = dz; a.bias = nullptr; a.nbias = 0; a.scale = scale; a.scale_group = d->scale_group; a.act = UEGAN_ACT_NONE;
+  a.Kp = (int)uegan_packed_k((int64_t)d->KH * d->KW * d->Cout);
+  a.w = w_ihwo; a.N = d->C1;
+  a.out = out; a.out2 = nullptr; a.n_out1 = d->C1;
+  a.frame = 0; a.fy0 = a.fy1 = a.fx0 = a.fx1 = 0; a.mask = nullptr; a.mask_act = UEGAN_ACT_NONE;
+}
+static bool dgrad_takes_tall(const uegan_conv_desc* d, const ConvArgs& a) {
+  const ConvGeom& g = a.g;
+  if (d->dtype != UEGAN_BF16 || d->C2 || g_conv_impl == UEGAN_IMPL_DIRECT || !g_use_glds || !g_use_patch || g_tuning[UEGAN_TUNE_VGG_EPI] == 0) return false;
+  if (dgrad_folds(d) || (g_use_heads && heads_dgrad_applicable(d))) return false;
+  if (g_use_stream && conv_toep_takes(a, d->dtype)) return false;
+  ConvStreamPlan sp;
+  if (conv_stream_plan(a, d->dtype, sp)) return false;
+  return g.stride == 1 && g.KH == 3 && g.KW == 3 && g.pad_mode != UEGAN_PAD_REFLECT && g.C % (CONV_ROWB / 2) == 0;
+}
+
+extern "C" int uegan_conv2d_dgrad_act_tap(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx1, int in_act,
+                                          const void* x_act, const void* y, float weight, const float* gscale, const float* tmp, int* applied,
+                                          uegan_stream_t stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  UEGAN_CHECK_ARG(dz && w_ihwo && dx1 && x_act && y && tmp && applied, "null pointer");
+  *applied = 0;
+  ConvArgs a;
+  dgrad_epi_args(d, dz, w_ihwo, scale, dx1, a);
+  a.mask = x_act; a.mask_act = in_act;              // (the unfused route: uegan_conv2d_dgrad_act's masked data gradient)
+  if (in_act != UEGAN_ACT_RELU || !dgrad_takes_tall(d, a)) return UEGAN_OK;
+  a.epi = 1;
+  a.epi_y = y; a.epi_weight = weight; a.epi_gscale = gscale;
+  percep_tap_consts(d->dtype, tmp, d->B, d->H * d->W, d->C1, &a.epi_st, &a.epi_tot);
+  rc = conv_tall_run(a, d->dtype, (hipStream_t)stream);
+  if (rc == 1) return UEGAN_OK;
+  if (rc == UEGAN_OK) *applied = 1;
+  return rc;
+}
+
+extern "C" int uegan_conv2d_dgrad_unpool(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx_full, int in_act,
+                                         const void* y_pool, const void* idx, int* applied, uegan_stream_t stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  UEGAN_CHECK_ARG(dz && w_ihwo && dx_full && y_pool && idx && applied, "null pointer");
+  *applied = 0;
+  ConvArgs a;
+  dgrad_epi_args(d, dz, w_ihwo, scale, dx_full, a);      // (the unfused route: uegan_conv2d_dgrad, no mask)
+  if (in_act != UEGAN_ACT_RELU || !dgrad_takes_tall(d, a)) return UEGAN_OK;
+  a.mask = y_pool; a.mask_act = in_act;
+  a.epi = 2;
+  a.epi_idx = static_cast<const unsigned char*>(idx);
+  rc = conv_tall_run(a, d->dtype, (hipStream_t)stream);
+  if (rc == 1) return UEGAN_OK;
+  if (rc == UEGAN_OK) *applied = 1;
+  return rc;
 }
 
 static void wgrad_plan(const uegan_conv_desc* d, WgradArgs& a, int& nsplit, dim3& grid, int& bn, WgradTrPlan& tr) {

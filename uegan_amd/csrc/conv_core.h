@@ -273,6 +273,18 @@ struct ConvArgs {
   int n_full = 1 << 30;         // with pool_out: images b >= n_full need only the POOLED result (no gradient will flow through them: the reference batch of the
                                // fidelity loss) -- a kernel with a pooling epilogue skips their full-resolution store; the others ignore this and write everything
   int xcd_map = 0;             // conv_wide_kernel: XCD-aware (tile, channel block) mapping (see there)
+  // conv_tall_kernel's data-gradient epilogues of the fidelity loss's backward (MODE 1 with a ReLU mask; uegan_conv2d_dgrad_act_tap / _unpool):
+  //   epi 1 (tap): the mask is a fidelity-loss tap; the epilogue adds its gradient against epi_y (percep_grad_kernel's term, common.h), with the
+  //                per-(image, channel) constants epi_st / epi_tot of its forward and weight * (*epi_gscale)
+  //   epi 2 (unpool): the mask is the 2x2 max-pool's output; the result goes through the window positions epi_idx (bytes, the mask's layout) to
+  //                `out` = the pool's INPUT gradient, [B][2 OH][2 OW][N], zero at the other three positions (maxpool2x2_bwd_idx_kernel)
+  int epi = 0;
+  const void* epi_y = nullptr;
+  const float* epi_st = nullptr;
+  const float* epi_tot = nullptr;
+  const float* epi_gscale = nullptr;
+  float epi_weight = 0.f;
+  const unsigned char* epi_idx = nullptr;
   // Reflection-padded stride-1 data gradients, split by conv_interior_run (conv_wide.hip): the pixel rectangle [rect_y0, rect_y1) x [rect_x0,
   // rect_x1) holds no pixel with a mirrored image; conv_wide_kernel / conv_tall_kernel compute it image-free (their tiles start at the
   // rectangle's origin), the patch kernel's MODE 2 launch then takes the frame around it (border_only)

@@ -12,4 +12,6 @@ bool heads_dgrad_applicable(const uegan_conv_desc* d);
 int heads_dgrad(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* dx, hipStream_t s);
 int heads_wgrad_blocks(const uegan_conv_desc* d);
 int heads_wgrad(const uegan_conv_desc* d, const void* x, const void* dz, float* ws, hipStream_t s);
+// norm_loss.hip: the per-(image, channel) constants of a fidelity-loss tap's backward inside its scratch (uegan_percep_tap_fwd's tmp)
+void percep_tap_consts(int dtype, const float* tmp, int B, int HW, int C, const float** st, const float** tot);
 }  // namespace uegan

@@ -349,6 +349,11 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
 //   consecutive rows from any first row.
 // MODE / MASK as conv_wide_kernel; POOL: the epilogue also writes the 2x2 max-pool of the tile (VGG conv1_2 / conv2_2; bit-identical to
 // pooling the stored tensor because rounding to bf16 is monotonic).
+// EPI (MODE 1, MASK with a ReLU; ConvArgs::epi): the elementwise pass that follows the data gradient in the fidelity loss's backward, folded
+// into the store loop.  1 (tap): + the tap's fidelity-loss gradient, read from the mask and epi_y with the store's 16-byte pattern
+// (percep_grad_kernel<..., RELU, ACC>: the same fp32 terms added in the same order, one rounding).  2 (unpool): the result is a max-pool's
+// output gradient (mask = the pooled tensor), scattered through the window positions to the four full-resolution pixels, zeros beside it
+// (maxpool2x2_bwd_idx_kernel); every store is still one pixel's BN contiguous channels.
 // RPW: tile rows per wave.  4: the 16-row tile above, 256 accumulator registers, one block per CU.  2 (128 channels only): an 8-row tile, 128
 // accumulator registers and <= 78 KB of LDS -- TWO blocks per CU, i.e. two waves per SIMD from different blocks: one block's prologue and
 // store-issue-bound epilogue (20 k of a 76-k-cycle tile, cycle stamps in DESIGN.md 3.1) run under the other block's K loop.
@@ -360,11 +365,12 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
 // hold such a row or column take the extra LDS reads (a scalar branch elsewhere).  This replaces the split into an image-free rectangle on
 // this kernel + a frame launch on conv_patch_kernel's MODE 2, where the mirrored images were extra MFMAs on masked fragments (+110 % on the
 // border tiles, 1.7 ms/step in round 4).
-template <int NI, int MODE, bool MASK, bool POOL, int RPW = 4>
+template <int NI, int MODE, bool MASK, bool POOL, int RPW = 4, int EPI = 0>
 __global__ void __launch_bounds__(256, RPW == 2 ? 2 : 1) conv_tall_kernel(ConvArgs a) {
   static_assert(RPW == 4 || RPW == 2, "rows per wave");
   constexpr bool REFL = MODE == 2;
   static_assert(!REFL || (NI == 4 && !MASK && !POOL), "mirrored images: 128-channel blocks, plain epilogue");
+  static_assert(EPI == 0 || (MODE == 1 && MASK && !POOL), "fidelity-loss epilogues: masked data gradients");
   constexpr int KS = 3, TH = 4 * RPW, TW = 32, BN = NI * 32, NWAVES = 4;
   constexpr int PH = TH + KS - 1, PW = TW + KS - 1, NPIX = PH * PW;
   constexpr int NPG = (NPIX + 15) / 16;                // 1-KB pieces (16 patch pixels x 64 B) of one patch buffer
@@ -664,6 +670,24 @@ __global__ void __launch_bounds__(256, RPW == 2 ? 2 : 1) conv_tall_kernel(ConvAr
   // ---- epilogue: scale, bias, activation in fp32 -> bf16 -> through the LDS (wave-private rows of BN channels + 8 B) -> NHWC rows,
   // 16 bytes per lane, BN/8 lanes per pixel (see conv_wide_kernel); the deferred activation gradient reads its mask the same way
   unsigned char* const est = lds + wave * (WPIX * EROW);
+  // EPI 1: the tap constants of my 8 store channels in image b (56 floats), requested here so that the staging below hides their latency
+  float tst[EPI == 1 ? 32 : 1], ttot[EPI == 1 ? 24 : 1], tgs = 1.f;
+  if constexpr (EPI == 1) {
+    const size_t bc = (size_t)g.B * a.N, o0 = (size_t)b * a.N + n0 + (lane % (BN / 8)) * 8;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.epi_st + (q >> 1) * bc + o0 + 4 * (q & 1));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tst[4 * q + e] = v[e];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.epi_tot + o0 * 3 + 4 * q);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ttot[4 * q + e] = v[e];
+    }
+    if (a.epi_gscale) tgs = *a.epi_gscale;
+  }
   {
     const float slope = a.act == UEGAN_ACT_LRELU ? 0.2f : (a.act == UEGAN_ACT_RELU ? 0.f : 1.f);
 #pragma unroll
@@ -698,6 +722,15 @@ __global__ void __launch_bounds__(256, RPW == 2 ? 2 : 1) conv_tall_kernel(ConvAr
     bf16_t* out = static_cast<bf16_t*>(a.out);
     const int lc = lane % LPP, nl = n0 + lc * 8;
     const int n_store = (POOL && b >= a.n_full) ? 0 : WPIX / PPI;      // (pooled result only: the store-bound half of this epilogue is skipped)
+    // EPI 1: percep_grad_kernel's constants of my channels (common.h, from the values requested before the staging)
+    float tmx[EPI == 1 ? 8 : 1], trx[EPI == 1 ? 8 : 1], tmy[EPI == 1 ? 8 : 1], try_[EPI == 1 ? 8 : 1], tmg[EPI == 1 ? 8 : 1], tmgx[EPI == 1 ? 8 : 1];
+    float tk = 0.f;
+    if constexpr (EPI == 1) {
+      float inv_n;
+      percep_scalars(a.epi_weight, &tgs, g.B, g.OH * g.OW, a.N, tk, inv_n);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) percep_consts(tst, ttot, 8, e, tk, inv_n, tmx[e], trx[e], tmy[e], try_[e], tmg[e], tmgx[e]);
+    }
 #pragma unroll 4
     for (int it = 0; it < n_store; ++it) {
       const int rr = it * PPI + lane / LPP;            // pixel inside the wave's 4 rows x 32 columns
@@ -710,12 +743,39 @@ __global__ void __launch_bounds__(256, RPW == 2 ? 2 : 1) conv_tall_kernel(ConvAr
       const size_t o = pix * a.N + nl;
       if (MASK) {
         const u32x4 m = *reinterpret_cast<const u32x4*>(static_cast<const bf16_t*>(a.mask) + o);
+        u32x4 yv = {0u, 0u, 0u, 0u};
+        if constexpr (EPI == 1) yv = *reinterpret_cast<const u32x4*>(static_cast<const bf16_t*>(a.epi_y) + o);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-          const float lo = half_lo_to_f32(v[d]) * (half_lo_to_f32(m[d]) > 0.f ? 1.f : mslope);
-          const float hi = half_hi_to_f32(v[d]) * (half_hi_to_f32(m[d]) > 0.f ? 1.f : mslope);
+          float lo = half_lo_to_f32(v[d]) * (half_lo_to_f32(m[d]) > 0.f ? 1.f : mslope);
+          float hi = half_hi_to_f32(v[d]) * (half_hi_to_f32(m[d]) > 0.f ? 1.f : mslope);
+          if constexpr (EPI == 1) {      // (percep_grad_kernel<..., RELU, ACC>: gx = (x > 0 ? g : 0) + gx)
+            const float xl = half_lo_to_f32(m[d]), xh = half_hi_to_f32(m[d]);
+            const float gl = percep_tap_grad(xl, half_lo_to_f32(yv[d]), tmx[2 * d], trx[2 * d], tmy[2 * d], try_[2 * d], tk, tmg[2 * d], tmgx[2 * d]);
+            const float gh = percep_tap_grad(xh, half_hi_to_f32(yv[d]), tmx[2 * d + 1], trx[2 * d + 1], tmy[2 * d + 1], try_[2 * d + 1], tk,
+                                             tmg[2 * d + 1], tmgx[2 * d + 1]);
+            lo = (xl > 0.f ? gl : 0.f) + lo;
+            hi = (xh > 0.f ? gh : 0.f) + hi;
+          }
           v[d] = pack_bf16x2(lo, hi);
         }
+      }
+      if constexpr (EPI == 2) {
+        // window position k = dy * 2 + dx of each channel's maximum (one byte per channel); channels 2d, 2d+1 = bytes 2(d&1), 2(d&1)+1 of word d>>1
+        const u32x2 a8 = *reinterpret_cast<const u32x2*>(a.epi_idx + o);
+        const size_t ow2 = 2 * (size_t)g.OW;
+        bf16_t* base = out + (((size_t)b * 2 * g.OH + 2 * oy) * ow2 + 2 * ox) * a.N + nl;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          u32x4 w4;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const uint32_t by = a8[d >> 1] >> (16 * (d & 1));
+            w4[d] = v[d] & (((by & 0xffu) == (uint32_t)k ? 0xffffu : 0u) | (((by >> 8) & 0xffu) == (uint32_t)k ? 0xffff0000u : 0u));
+          }
+          *reinterpret_cast<u32x4*>(base + ((k >> 1) * ow2 + (k & 1)) * a.N) = w4;
+        }
+        continue;
       }
       bf16_t* dst = !a.out2 ? out + o : (nl < a.n_out1 ? out + pix * a.n_out1 + nl : static_cast<bf16_t*>(a.out2) + pix * (a.N - a.n_out1) + (nl - a.n_out1));
       *reinterpret_cast<u32x4*>(dst) = v;
@@ -776,6 +836,7 @@ int conv_tall_run(ConvArgs& a, int dtype, hipStream_t s, bool interior) {
   if (interior && (g.mode != 1 || g.C2 || a.mask || (a.out2 && a.n_out1 % 8))) return 1;
   auto simple = [](int act) { return act == UEGAN_ACT_NONE || act == UEGAN_ACT_LRELU || act == UEGAN_ACT_RELU; };
   if (!simple(a.act) || (a.mask && !simple(a.mask_act))) return 1;
+  if (a.epi && (interior || refl || g.mode != 1 || !a.mask || a.mask_act != UEGAN_ACT_RELU || a.out2 || g.C2)) return 1;      // (fidelity-loss epilogues)
   // 128-channel blocks: 8-row tiles, two blocks per CU (RPW = 2) while the K loop is short (< 512 input channels: the prologue and epilogue
   // are then 25 % and more of a tile, and the second block hides them: -5 ... -31 % per layer); at 512 input channels the 16-row tile's
   // lower LDS traffic per MFMA wins by 2 ... 5 %.  UEGAN_TUNE_TALL_RPW = 2 / 4 forces one of them (A/B, tests).
@@ -804,6 +865,8 @@ int conv_tall_run(ConvArgs& a, int dtype, hipStream_t s, bool interior) {
   do {                                                                                                               \
     if (g.mode == 0 && pool) hipLaunchKernelGGL((conv_tall_kernel<NI, 0, false, true, RPW>), grid, block, 0, s, a);  \
     else if (g.mode == 0) hipLaunchKernelGGL((conv_tall_kernel<NI, 0, false, false, RPW>), grid, block, 0, s, a);    \
+    else if (a.mask && a.epi == 1) hipLaunchKernelGGL((conv_tall_kernel<NI, 1, true, false, RPW, 1>), grid, block, 0, s, a); \
+    else if (a.mask && a.epi == 2) hipLaunchKernelGGL((conv_tall_kernel<NI, 1, true, false, RPW, 2>), grid, block, 0, s, a); \
     else if (a.mask) hipLaunchKernelGGL((conv_tall_kernel<NI, 1, true, false, RPW>), grid, block, 0, s, a);          \
     else hipLaunchKernelGGL((conv_tall_kernel<NI, 1, false, false, RPW>), grid, block, 0, s, a);                     \
   } while (0)

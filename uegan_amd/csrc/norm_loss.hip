@@ -6,6 +6,7 @@
 // GANLoss 'rahinge' (losses.py:348-362, 393-409), MultiscaleRecLoss (losses.py:219-231),
 // PerceptualLoss tap term (losses.py:30-34).
 #include "common.h"
+#include "conv_internal.h"
 
 namespace uegan {
 
@@ -441,25 +442,20 @@ __global__ void percep_grad_kernel(const T* x, const T* y, const float* st, cons
                                    RedPlan p, int act) {       // ACC: gx += ... (the tap has a second consumer whose gradient is already in gx)
   RED_THREAD_SETUP();
   if (!cvalid) return;
-  const float nel = (float)p.B * (float)p.HW * (float)p.C;
-  // g = dL/dxh = k*(xh-yh), k = 2*weight*gscale/nel ; dx = rx*(g - mean(g) - xh*mean(g*xh))
-  const float k = 2.f * weight * (gscale ? *gscale : 1.f) / nel, inv_n = 1.f / (float)p.HW;
+  // (the formula lives in common.h: conv_tall_kernel's tap epilogue evaluates the same one, bit for bit)
+  float k, inv_n;
+  percep_scalars(weight, gscale, p.B, p.HW, p.C, k, inv_n);
   const size_t bc = (size_t)p.B * p.C, o0 = (size_t)b * p.C + c0;
   float mx[V], rx[V], my[V], ry[V], mg[V], mgx[V];
 #pragma unroll
-  for (int e = 0; e < V; ++e) {
-    mx[e] = st[o0 + e]; rx[e] = st[bc + o0 + e]; my[e] = st[2 * bc + o0 + e]; ry[e] = st[3 * bc + o0 + e];
-    mg[e] = k * tot[(o0 + e) * 3 + 1] * inv_n;
-    mgx[e] = k * tot[(o0 + e) * 3 + 2] * inv_n;
-  }
+  for (int e = 0; e < V; ++e) percep_consts(st, tot, bc, o0 + e, k, inv_n, mx[e], rx[e], my[e], ry[e], mg[e], mgx[e]);
   _Pragma("unroll 4") for (int q = p0 + pl; q < p1; q += p.PL) {
     float xv[V], yv[V];
     Vec<T, V>::ld(x + base + (size_t)q * p.C, xv);
     Vec<T, V>::ld(y + base + (size_t)q * p.C, yv);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const float xh = (xv[e] - mx[e]) * rx[e], yh = (yv[e] - my[e]) * ry[e];
-      const float gv = rx[e] * (k * (xh - yh) - mg[e] - xh * mgx[e]);
+      const float gv = percep_tap_grad(xv[e], yv[e], mx[e], rx[e], my[e], ry[e], k, mg[e], mgx[e]);
       xv[e] = RELU ? (xv[e] > 0.f ? gv : 0.f) : gv * act_grad_from_out(xv[e], act);      // (act: x's producer's deferred act')
     }
     if (ACC) {
@@ -1115,6 +1111,14 @@ static void percep_layout(const RedPlan& p, float* tmp, float*& px, float*& py, 
   px = tmp; py = tmp + region; sums = tmp + 2 * region;
   st = tmp + part;
   tot = tmp + 2 * region + part;
+}
+// where the backward's constants sit in a tap's scratch (conv.hip: uegan_conv2d_dgrad_act_tap hands them to conv_tall_kernel's tap epilogue)
+void uegan::percep_tap_consts(int dtype, const float* tmp, int B, int HW, int C, const float** st, const float** tot) {
+  RedPlan p = make_plan(B, HW, C, epc_of(dtype));
+  float *px, *py, *sums, *s, *t;
+  percep_layout(p, const_cast<float*>(tmp), px, py, sums, s, t);
+  *st = s;
+  *tot = t;
 }
 
 extern "C" int uegan_percep_tap_fwd(int dtype, const void* x, const void* y, float weight, float* loss, float* tmp, int B, int HW, int C,

@@ -106,9 +106,12 @@ class _VGGFidelityFn(torch.autograd.Function):
         st = _stream()
         cur = None               # d loss / d (current activation), first B images, ALREADY multiplied by relu'(activation)
         ti = len(ctx.taps) - 1
+        folded = set()           # records whose backward pass the data gradient behind them ran in its epilogue (_dgrad_tap / _dgrad_unpool)
         for li in range(len(ctx.recs) - 1, -1, -1):
             kind, xin, d, ihwo, is_tap = ctx.recs[li]
             if kind == "pool":
+                if li in folded:
+                    continue     # cur is already the gradient of the pool's input
                 yp, pidx, (Bt, H, W, Cc) = d
                 gx = torch.empty((B, H, W, Cc), dtype=yp.dtype, device=yp.device)
                 # the pool's input is a ReLU output whose act' was deferred to its consumers: applied here
@@ -118,7 +121,9 @@ class _VGGFidelityFn(torch.autograd.Function):
                     L.check(lib().uegan_maxpool2x2_bwd_act(_dt(xin), ACT_RELU, _p(xin), _p(cur), _p(gx), B, H, W, Cc, st))
                 cur = gx
                 continue
-            if is_tap:
+            if is_tap and li in folded:
+                ti -= 1
+            elif is_tap:
                 t, tmp, w = ctx.taps[ti], ctx.tmps[ti], ctx.weights[ti]
                 ti -= 1
                 _, H, W, Cc = t.shape
@@ -134,9 +139,47 @@ class _VGGFidelityFn(torch.autograd.Function):
             if li == 0:
                 dx, _ = ops.raw_conv_dgrad(d, cur, ihwo, nb=B)        # the image itself: no activation in front
                 return ops.raw_to_nchw_grad(dx, ctx.C, ctx.a), None, None, None, None, None, None
-            prev_is_conv = ctx.recs[li - 1][0] == "conv"
+            prev = ctx.recs[li - 1]
+            prev_is_conv = prev[0] == "conv"
+            if prev_is_conv and prev[4]:
+                # a tap in front (its gradient accumulates onto this one, acc = 1): added by this data gradient's epilogue where a kernel can
+                ty = ctx.taps[ti][B:] if ctx.ytaps is None else ctx.ytaps[ti]
+                dx = _dgrad_tap(d, cur, ihwo, xin, ty, ctx.weights[ti], g, ctx.tmps[ti], B)
+                if dx is not None:
+                    cur = dx
+                    folded.add(li - 1)
+                    continue
+            elif not prev_is_conv and prev[2][1] is not None:
+                # a max-pool in front with its window positions stored: this data gradient's epilogue writes the pool's input gradient
+                yp, pidx, (Bt, H, W, Cc) = prev[2]
+                gx = _dgrad_unpool(d, cur, ihwo, yp, pidx, (B, H, W, Cc), B)
+                if gx is not None:
+                    cur = gx
+                    folded.add(li - 1)
+                    continue
             cur, _ = ops.raw_conv_dgrad(d, cur, ihwo, in_act=ACT_RELU if prev_is_conv else ACT_NONE, x_act=xin if prev_is_conv else None, nb=B)
         raise RuntimeError("VGG plan does not start with a convolution")
+
+
+def _dgrad_tap(d, dz, ihwo, t, ty, w, g, tmp, nb):
+    """uegan_conv2d_dgrad_act_tap: dgrad(dz) * relu'(t) + the fidelity-loss gradient of tap t against ty (first nb images) in ONE launch --
+    the data gradient, or None where the library declines (the caller then runs raw_conv_dgrad + uegan_percep_tap_bwd_acc)"""
+    d = ops._sub_desc(d, nb)
+    dx = torch.empty((d.B, d.H, d.W, d.C1), dtype=dz.dtype, device=dz.device)
+    ok = C.c_int(0)
+    L.check(lib().uegan_conv2d_dgrad_act_tap(C.byref(d), _p(dz), _p(ihwo), None, _p(dx), ACT_RELU, _p(t), _p(ty), float(w), _p(g), _p(tmp),
+                                             C.byref(ok), _stream()))
+    return dx if ok.value else None
+
+
+def _dgrad_unpool(d, dz, ihwo, yp, pidx, full_shape, nb):
+    """uegan_conv2d_dgrad_unpool: the gradient of the 2x2 max-pool's INPUT (shape full_shape) from dgrad(dz) -- the gradient of its output -- in
+    ONE launch, or None where the library declines (the caller then runs raw_conv_dgrad + uegan_maxpool2x2_bwd_idx)"""
+    d = ops._sub_desc(d, nb)
+    gx = torch.empty(full_shape, dtype=dz.dtype, device=dz.device)
+    ok = C.c_int(0)
+    L.check(lib().uegan_conv2d_dgrad_unpool(C.byref(d), _p(dz), _p(ihwo), None, _p(gx), ACT_RELU, _p(yp), _p(pidx), C.byref(ok), _stream()))
+    return gx if ok.value else None
 
 
 def vgg_fidelity_loss(vgg, weights, x, y, a, b, y_taps=None):
