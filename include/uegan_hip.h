@@ -366,6 +366,40 @@ int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, double*
 int uegan_input_transform(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
                           const int32_t* vtab, int vk, const int32_t* flips, uint8_t* tmp, float* out_nchw, uegan_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * NIMA aesthetic scorer (metrics/NIMA/CalcNIMA.py: MobileNetV2 trunk + ReLU -> Linear(1280, 10) -> Softmax), eval mode, fp32 only.
+ * Activations are fp32 NHWC with the channel count padded to a multiple of 16; padded channels have zero weights and zero shift and
+ * stay exactly 0.  Eval BatchNorm is folded by the caller into (scale, shift) per output channel; every convolution computes
+ *   y = clamp(acc * scale[c] + shift[c], lo, hi)      (0, 6): ReLU6   (0, +inf): ReLU   (-inf, +inf): no activation
+ * All pointers are DEVICE fp32 and 16-byte aligned; nothing here needs scratch memory.
+ * ------------------------------------------------------------------------------------------------- */
+/* Preparation (CalcNIMA.py:45-55: Resize(256), CenterCrop(224), ToTensor) of B decoded 8-bit RGB images [B][in_h][in_w][3]: Pillow's
+ * two-pass resampler as in uegan_input_transform, with the crop folded into the tables (htab / vtab point at the rows of the out_w /
+ * out_h KEPT output indices) and v / 255 as the value.  cpad == 0: out is NCHW [B][3][out_h][out_w]; cpad >= 3: NHWC
+ * [B][out_h][out_w][cpad] with the channels past 3 zeroed.  tmp: DEVICE uint8 [B][in_h][out_w][3].  Bit-exact with Pillow. */
+int uegan_nima_prepare(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
+                       const int32_t* vtab, int vk, uint8_t* tmp, float* out, int cpad, uegan_stream_t stream);
+/* First layer: 3x3 convolution, zero padding 1, stride 1 or 2, of a 3-channel image read through element strides (NCHW: stride_c = H*W,
+ * stride_y = W, stride_x = 1; NHWC with cpad channels: stride_c = 1, stride_y = W*cpad, stride_x = cpad).  w_kc: [27][Cout_pad] with
+ * row (ky*3 + kx)*3 + ci.  y_nhwc: [B][Ho][Wo][Cout_pad], Ho = (H-1)/stride + 1. */
+int uegan_nima_conv3x3_first(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x, const float* w_kc,
+                             const float* scale, const float* shift, float* y_nhwc, int B, int H, int W, int Cout_pad, int stride,
+                             float lo, float hi, uegan_stream_t stream);
+/* Depthwise (groups == C) 3x3 convolution, zero padding 1, stride 1 or 2.  w_9c: [9][C_pad] with row ky*3 + kx.
+ * x_nhwc [B][H][W][C_pad] -> y_nhwc [B][Ho][Wo][C_pad]. */
+int uegan_nima_dwconv3x3(const float* x_nhwc, const float* w_9c, const float* scale, const float* shift, float* y_nhwc, int B, int H, int W,
+                         int C_pad, int stride, float lo, float hi, uegan_stream_t stream);
+/* Pointwise 1x1 convolution as a GEMM on the matrix cores: x_mk [M][Cin_pad] (M = B*H*W pixels), w_nk [Cout_pad][Cin_pad] (the
+ * convolution's own [Cout][Cin] layout, zero-padded) -> y_mn [M][Cout_pad].  residual (may be NULL): [M][Cout_pad], added AFTER the
+ * affine and the clamp (x + conv(x), mobile_net_v2.py:51-52). */
+int uegan_nima_pwconv(const float* x_mk, const float* w_nk, const float* scale, const float* shift, const float* residual, float* y_mn,
+                      int64_t M, int Cin_pad, int Cout_pad, float lo, float hi, uegan_stream_t stream);
+/* Head: mean over the HW pixels of x_nhwc [B][HW][C_pad] -> ReLU -> Linear (w [n_classes][C], bias [n_classes]) -> softmax.  Per image:
+ * probs [B][n_classes], mean[b] = sum_j j * p_j and std[b] = sqrt(sum_j p_j * (j - mean)^2) over j = 1..n_classes (CalcNIMA.py:86-91);
+ * pooled (may be NULL) [B][C]: the pooled vector before the ReLU.  C <= 2048, n_classes <= 16. */
+int uegan_nima_head(const float* x_nhwc, const float* w, const float* bias, float* pooled, float* probs, float* mean, float* std, int B,
+                    int HW, int C_pad, int C, int n_classes, uegan_stream_t stream);
+
 /* Device-scalar plumbing of the step driver: zero a buffer (gradient buckets, loss accumulators); total[0] = sum_i weights[i] * terms[i][0]
  * accumulated left to right (trainer.py:104-115: g_loss = lambda_adv*adv + lambda_percep*percep + lambda_idt*idt), scaled[i] (may be NULL) =
  * weights[i] * terms[i][0] (the logged per-term values); its backward gout[i] = weights[i] * g[0].  terms: HOST table of device pointers. */

@@ -66,9 +66,57 @@ __global__ void resample_v_norm_kernel(const uint8_t* tmp, float* out, const int
   }
 }
 
+// pass 2 of the NIMA preparation (CalcNIMA.py:45-55: Resize(256) -> CenterCrop(224) -> ToTensor): the crop is an offset into the two tables
+// (the caller passes the rows of the kept output indices only), the value is ToTensor's v / 255 alone.  cpad == 0: NCHW planes;
+// cpad >= 3: NHWC with cpad channels per pixel, the extra ones zero.
+__global__ void resample_v_unit_kernel(const uint8_t* tmp, float* out, const int32_t* tab, int K, int B, int H, int OH, int OW, int cpad) {
+  const size_t total = (size_t)B * OH * OW;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % OW);
+    const size_t r = i / OW;
+    const int yo = (int)(r % OH), b = (int)(r / OH);
+    const int32_t* t = tab + (size_t)yo * (K + 2);
+    const int y0 = t[0], n = t[1];
+    const uint8_t* p = tmp + (((size_t)b * H + y0) * OW + xo) * 3;
+    int s0 = 1 << (RESAMPLE_PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int k = 0; k < n; ++k) {
+      const int c = t[2 + k];
+      const uint8_t* pk = p + (size_t)k * OW * 3;
+      s0 += pk[0] * c; s1 += pk[1] * c; s2 += pk[2] * c;
+    }
+    const int v[3] = {clip8(s0 >> RESAMPLE_PRECISION_BITS), clip8(s1 >> RESAMPLE_PRECISION_BITS), clip8(s2 >> RESAMPLE_PRECISION_BITS)};
+    if (cpad == 0) {
+      const size_t plane = (size_t)OH * OW;
+      float* o = out + (((size_t)b * 3) * OH + yo) * OW + xo;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c * plane] = __fdiv_rn((float)v[c], 255.f);
+    } else {
+      float* o = out + i * cpad;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c] = __fdiv_rn((float)v[c], 255.f);
+      for (int c = 3; c < cpad; ++c) o[c] = 0.f;
+    }
+  }
+}
+
 }  // namespace uegan
 
 using namespace uegan;
+
+extern "C" int uegan_nima_prepare(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
+                                  const int32_t* vtab, int vk, uint8_t* tmp, float* out, int cpad, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(pixels && htab && vtab && tmp && out, "nima_prepare: null pointer");
+  UEGAN_CHECK_ARG(B >= 1 && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0 && hk >= 1 && vk >= 1, "nima_prepare: bad geometry");
+  UEGAN_CHECK_ARG(cpad == 0 || cpad >= 3, "nima_prepare: cpad is 0 (NCHW) or the NHWC channel count >= 3 (got %d)", cpad);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n1 = (size_t)B * in_h * out_w, n2 = (size_t)B * out_h * out_w;
+  const int b1 = (int)((n1 + 255) / 256 < 16384 ? (n1 + 255) / 256 : 16384), b2 = (int)((n2 + 255) / 256 < 16384 ? (n2 + 255) / 256 : 16384);
+  hipLaunchKernelGGL(resample_h_kernel, dim3(b1), dim3(256), 0, s, pixels, tmp, htab, hk, B, in_h, in_w, out_w);
+  UEGAN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(resample_v_unit_kernel, dim3(b2), dim3(256), 0, s, (const uint8_t*)tmp, out, vtab, vk, B, in_h, out_h, out_w, cpad);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
 
 extern "C" int uegan_input_transform(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
                                      const int32_t* vtab, int vk, const int32_t* flips, uint8_t* tmp, float* out_nchw, uegan_stream_t stream) {

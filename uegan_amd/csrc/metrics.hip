@@ -4,6 +4,7 @@
 // metrics/CalcSSIM.py:63 (7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance, data_range 255, mean over the three
 // channels) -- all on the device, so validation never copies images to the host.
 #include "common.h"
+#include "nima.h"      // the NIMA scorer's kernels (MobileNetV2 trunk + head), entry points at the end of this file
 
 namespace uegan {
 
@@ -241,5 +242,57 @@ extern "C" int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nh
     hipLaunchKernelGGL(ssim_fix_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ssim_sum, B);
     UEGAN_CHECK_LAUNCH();
   }
+  return UEGAN_OK;
+}
+
+// ---- NIMA scorer (nima.h): fp32 NHWC tensors whose channel counts are multiples of 16 ----
+static bool nima_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int uegan_nima_conv3x3_first(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x, const float* w_kc,
+                                        const float* scale, const float* shift, float* y_nhwc, int B, int H, int W, int Cout_pad, int stride,
+                                        float lo, float hi, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x && w_kc && scale && shift && y_nhwc, "nima_conv3x3_first: null pointer");
+  UEGAN_CHECK_ARG(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "nima_conv3x3_first: bad geometry");
+  UEGAN_CHECK_ARG(Cout_pad > 0 && Cout_pad % NIMA_CPAD == 0, "nima_conv3x3_first: Cout_pad must be a multiple of %d (got %d)", NIMA_CPAD, Cout_pad);
+  UEGAN_CHECK_ARG(stride_b >= 0 && stride_c > 0 && stride_y > 0 && stride_x > 0, "nima_conv3x3_first: bad input strides");
+  UEGAN_CHECK_ARG(nima_aligned(w_kc) && nima_aligned(scale) && nima_aligned(shift) && nima_aligned(y_nhwc), "nima_conv3x3_first: 16-byte alignment");
+  nima_first_launch(x, stride_b, stride_c, stride_y, stride_x, w_kc, scale, shift, y_nhwc, B, H, W, Cout_pad, stride, lo, hi, (hipStream_t)stream);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_nima_dwconv3x3(const float* x_nhwc, const float* w_9c, const float* scale, const float* shift, float* y_nhwc, int B, int H, int W,
+                                    int C_pad, int stride, float lo, float hi, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x_nhwc && w_9c && scale && shift && y_nhwc, "nima_dwconv3x3: null pointer");
+  UEGAN_CHECK_ARG(B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "nima_dwconv3x3: bad geometry");
+  UEGAN_CHECK_ARG(C_pad > 0 && C_pad % NIMA_CPAD == 0, "nima_dwconv3x3: C_pad must be a multiple of %d (got %d)", NIMA_CPAD, C_pad);
+  UEGAN_CHECK_ARG(nima_aligned(x_nhwc) && nima_aligned(w_9c) && nima_aligned(scale) && nima_aligned(shift) && nima_aligned(y_nhwc),
+                  "nima_dwconv3x3: 16-byte alignment");
+  UEGAN_CHECK_ARG((size_t)B * H * W * (C_pad / 4) < ((size_t)1 << 31) * 256, "nima_dwconv3x3: tensor too large");
+  nima_dw_launch(x_nhwc, w_9c, scale, shift, y_nhwc, B, H, W, C_pad, stride, lo, hi, (hipStream_t)stream);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_nima_pwconv(const float* x_mk, const float* w_nk, const float* scale, const float* shift, const float* residual, float* y_mn,
+                                 int64_t M, int Cin_pad, int Cout_pad, float lo, float hi, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x_mk && w_nk && scale && shift && y_mn, "nima_pwconv: null pointer");
+  UEGAN_CHECK_ARG(M > 0 && M <= (int64_t)65535 * 16, "nima_pwconv: 1..%d rows per call (got %lld)", 65535 * 16, (long long)M);
+  UEGAN_CHECK_ARG(Cin_pad > 0 && Cin_pad % NIMA_CPAD == 0 && Cout_pad > 0 && Cout_pad % NIMA_CPAD == 0,
+                  "nima_pwconv: channel counts must be multiples of %d (got %d -> %d)", NIMA_CPAD, Cin_pad, Cout_pad);
+  UEGAN_CHECK_ARG(nima_aligned(x_mk) && nima_aligned(w_nk) && nima_aligned(scale) && nima_aligned(shift) && nima_aligned(y_mn) && nima_aligned(residual),
+                  "nima_pwconv: 16-byte alignment");
+  nima_pw_launch(x_mk, w_nk, scale, shift, residual, y_mn, (int)M, Cin_pad, Cout_pad, lo, hi, (hipStream_t)stream);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_nima_head(const float* x_nhwc, const float* w, const float* bias, float* pooled, float* probs, float* mean, float* std, int B,
+                               int HW, int C_pad, int C, int n_classes, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x_nhwc && w && bias && probs && mean && std, "nima_head: null pointer");
+  UEGAN_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C <= C_pad && C <= NIMA_HEAD_MAX_C, "nima_head: 1..%d channels (got %d of %d)", NIMA_HEAD_MAX_C, C, C_pad);
+  UEGAN_CHECK_ARG(n_classes >= 1 && n_classes <= NIMA_HEAD_MAX_CLS, "nima_head: 1..%d classes (got %d)", NIMA_HEAD_MAX_CLS, n_classes);
+  hipLaunchKernelGGL(nima_head_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x_nhwc, w, bias, pooled, probs, mean, std, HW, C_pad, C, n_classes);
+  UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }

@@ -9,7 +9,8 @@
                                       border crop both scripts apply (:24,56), computed by libuegan_hip.so kernels
     mean_metric(values)               the TRUE mean; the reference's directory averages divide by N-1 (CalcPSNR.py:77, CalcSSIM.py:75)
     run_test(G, loader, ...)          the loop of Tester.test (tester.py:40-105): enhance every batch of a test loader, write the
-                                      PNGs `save_image` would write, PSNR / SSIM against the labels on the device
+                                      PNGs `save_image` would write, PSNR / SSIM against the labels on the device, and the NIMA
+                                      score of the enhanced images (uegan_amd/nima.py) when a scorer is passed
 """
 import math
 
@@ -123,7 +124,7 @@ def mean_metric(values):
     return sum(values) / len(values)
 
 
-def run_test(G, loader, save_dir=None, tag="0.00", metrics=True):
+def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None):
     """Tester.test (tester.py:40-105) over a `uegan_amd.data` test loader: `G.eval()` forward per batch (:64-67), the enhanced image of
     every sample as `<name>_<tag>_testFakeExp.png` in `save_dir` (:69-71: the 8-bit image torchvision's save_image writes; None: no
     files), and -- what calc_psnr / calc_ssim then compute from those files against the label images (:96-103) -- PSNR and SSIM of
@@ -134,9 +135,15 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True):
     (data_loader.py:95-99) and re-quantised to 8 bits -- whereas calc_psnr / calc_ssim read the ORIGINAL files of test_label_dir.  The
     numbers agree with the reference's when the label files already have the test size (the reference itself needs equal shapes:
     CalcPSNR.py:87 raises otherwise); for labels of another size decode them yourself and call calculate_psnr / calculate_ssim.  The
-    test_compare montage images (tester.py:73-90) are not written."""
+    test_compare montage images (tester.py:73-90) are not written.
+
+    nima: a `uegan_amd.nima.NIMA` module -> also "nima" / "nima_std" (per image) and "mean_nima" (true mean): what calc_nima (tester.py:91-94,
+    on by default in the reference: config.py:80) computes from the saved files, here from the same 8-bit images on the device.  It needs no
+    label: with metrics=False the loader's `img_exp` is never touched (the unpaired setting)."""
     import os
-    names, psnr, ssim = [], [], []
+    names, psnr, ssim, nima_mean, nima_std = [], [], [], [], []
+    if nima is not None:
+        from . import nima as nima_mod
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
     for batch in loader:
@@ -146,6 +153,10 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True):
             ref = to_uint8_image(batch.img_exp)
             psnr += calculate_psnr(q, ref)
             ssim += calculate_ssim(q, ref)
+        if nima is not None:
+            m, d = nima_mod.score(nima, q)
+            nima_mean += m
+            nima_std += d
         names += list(batch.img_name)
         if save_dir is not None:
             from PIL import Image
@@ -155,4 +166,8 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True):
     out = {"names": names, "psnr": psnr, "ssim": ssim}
     if metrics and names:
         out["mean_psnr"], out["mean_ssim"] = mean_metric(psnr), mean_metric(ssim)
+    if nima is not None:
+        out["nima"], out["nima_std"] = nima_mean, nima_std
+        if names:
+            out["mean_nima"] = mean_metric(nima_mean)
     return out
