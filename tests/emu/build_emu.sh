@@ -11,15 +11,14 @@ build_one() {      # <object dir> <output .so> <extra flags...>
   local OUT="$1" LIB="$2"; shift 2
   mkdir -p "$OUT"
   local pids=() OBJS=() rc=0
-  for s in conv conv_stream_ex conv_patch_bf16_a conv_patch_bf16_b conv_patch_f32_a conv_patch_f32_b conv_s2 conv_wide conv_flat conv_toep heads heads_mfma elementwise norm_loss optim_sn metrics input; do
-    local o="$OUT/$s.o"
+  for src in "$ROOT"/uegan_amd/csrc/*.hip; do      # the product's unit list: uegan_amd/csrc/build.sh globs the same directory
+    local o="$OUT/$(basename "${src%.hip}").o"
     OBJS+=("$o")
-    local src="$ROOT/uegan_amd/csrc/$s.hip"
     local stale=0
     if [ ! -f "$o" ] || [ "$src" -nt "$o" ]; then stale=1; fi
     for h in "${HDRS[@]}"; do if [ "$h" -nt "$o" ]; then stale=1; fi; done
     if [ "$stale" = 1 ]; then
-      "$CXX" -x c++ -std=c++17 -O2 -g -fPIC -pthread -I"$HERE" -Wno-unused-function -Wno-reserved-identifier "$@" -c "$src" -o "$o" &
+      "$CXX" -x c++ -std=c++17 -O2 -g -fPIC -pthread -I"$HERE" -Wno-unused-function -Wno-reserved-identifier -DUEGAN_EMU_UNITS "$@" -c "$src" -o "$o" &
       pids+=($!)
     fi
   done

@@ -7,20 +7,20 @@ HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="${1:-$HERE/../libuegan_hip.so}"
 OUT16="${2:-$(dirname "$OUT")/libuegan_hip_f16.so}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-SRCS=(conv.hip conv_stream_ex.hip conv_patch_bf16_a.hip conv_patch_bf16_b.hip conv_patch_f32_a.hip conv_patch_f32_b.hip conv_s2.hip conv_wide.hip conv_flat.hip conv_toep.hip heads.hip heads_mfma.hip elementwise.hip norm_loss.hip optim_sn.hip metrics.hip input.hip)
+SRCS=("$HERE"/*.hip)      # every unit of this directory (tests/emu/build_emu.sh and tools/build_tools.sh glob it as well)
 HDRS=("$HERE"/*.h "$HERE/../../include/uegan_hip.h")
 build_one() {      # <object dir> <output .so> <extra flags...>
   local odir="$1" out="$2"; shift 2
   local objs=() pids=() rc=0
   mkdir -p "$odir"
   for s in "${SRCS[@]}"; do
-    local o="$odir/${s%.hip}.o"
+    local o="$odir/$(basename "${s%.hip}").o"
     objs+=("$o")
     local stale=0
-    if [ ! -f "$o" ] || [ "$HERE/$s" -nt "$o" ]; then stale=1; fi
+    if [ ! -f "$o" ] || [ "$s" -nt "$o" ]; then stale=1; fi
     for h in "${HDRS[@]}"; do if [ "$h" -nt "$o" ]; then stale=1; fi; done
     if [ "$stale" = 1 ]; then
-      "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno-unused-function "$@" -c "$HERE/$s" -o "$o" &
+      "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno-unused-function "$@" -c "$s" -o "$o" &
       pids+=($!)
     fi
   done

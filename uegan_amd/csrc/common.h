@@ -18,7 +18,7 @@
 
 namespace uegan {
 
-extern int g_tuning[UEGAN_TUNE_COUNT];      // uegan_set_tuning (conv.hip): launch-variant thresholds; the library never reads the environment
+extern int g_tuning[UEGAN_TUNE_COUNT];      // uegan_set_tuning (runtime.hip): launch-variant thresholds; the library never reads the environment
 extern int g_abl_stream, g_abl_wide;        // tools build only (always 0 in the product)
 
 

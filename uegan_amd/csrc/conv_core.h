@@ -1,4 +1,4 @@
-// Shared pieces of the convolution translation units (conv.hip, conv_patch_*.hip): launch-timing scope, MFMA wrappers,
+// Shared pieces of the convolution translation units (conv*.hip, wgrad.hip, ...): launch-timing scope, MFMA wrappers,
 // gather geometry, the argument block of the gather-GEMM kernels.  Internal (non-ABI).
 #pragma once
 #include "common.h"
@@ -108,15 +108,12 @@ template <> __device__ __forceinline__ u32x4 add_frag<float>(u32x4 a, u32x4 b) {
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
   static constexpr int NCHUNK = 1;  // 16B chunks per lane per 32-wide K step
-  // lane (r=l&15, g=l>>4) reads elements k = 8g..8g+7
-  static __device__ __forceinline__ int chunk_byte(int g, int /*c*/) { return g * 16; }
   static __device__ __forceinline__ void step(const u32x4* a, const u32x4* b, f32x4& acc) { acc = mfma_bf16(a[0], b[0], acc); }
 };
 template <> struct Mma<float> {
   static constexpr int NCHUNK = 2;
   // chunk c covers k = 16c + 4g .. 16c + 4g + 3; element j of the chunk feeds MFMA #j of that chunk.  Both
   // operands use the same k permutation, so the sum over k is unchanged.
-  static __device__ __forceinline__ int chunk_byte(int g, int c) { return (c * 16 + g * 4) * 4; }
   static __device__ __forceinline__ void step(const u32x4* a, const u32x4* b, f32x4& acc) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -349,5 +346,37 @@ int splitk_reduce_launch(const ConvArgs& a, hipStream_t s);
 
 constexpr int CONV_TH = 8, CONV_TW = 16, CONV_BM = CONV_TH * CONV_TW;
 constexpr int CONV_ROWB = 128;   // bytes per LDS row = one K step
+
+// Implementation switches (runtime.hip): uegan_set_conv_impl is the only writer.  impl: AUTO / MFMA / DIRECT; the flags: direct-to-LDS staging,
+// the patch-resident kernel family, the narrow-head kernels, the transpose-read weight gradient, the streaming / Toeplitz kernels.
+struct ConvImpl { int impl; bool glds, patch, heads, wgtr, stream; };
+extern ConvImpl g_impl;
+
+// ---- what the convolution units call of each other.  A *_run returns 1 when its kernel does not take the layer (nothing launched).
+// conv.hip: descriptor check (sets the error text) and the forward gather geometry of a descriptor
+int check_desc(const uegan_conv_desc* d);
+ConvGeom fwd_geom(const uegan_conv_desc* d);
+static inline int cin_w(const uegan_conv_desc* d) { return d->Cin_w ? d->Cin_w : d->C1 + d->C2; }
+static inline int cin_row(const uegan_conv_desc* d) { return d->Cin_total ? d->Cin_total : cin_w(d); }
+static inline int cout_w(const uegan_conv_desc* d) { return d->Cout_w ? d->Cout_w : d->Cout; }
+// conv_gemm.hip: the generic gather-GEMM kernel (GLDS or register staged, as g_impl says), or the scalar direct kernel under UEGAN_IMPL_DIRECT
+int conv_gemm_run(ConvArgs& a, int dtype, hipStream_t s);
+// patch-resident kernel instantiations live in conv_patch_{bf16,f32}_{a,b}.hip (a: KS 1..3, b: KS 4, 5, 7); 1 = no such KS
+int conv_patch_bf16_a(ConvArgs& a, hipStream_t s, int ks);
+int conv_patch_bf16_b(ConvArgs& a, hipStream_t s, int ks);
+int conv_patch_f32_a(ConvArgs& a, hipStream_t s, int ks);
+int conv_patch_f32_b(ConvArgs& a, hipStream_t s, int ks);
+int conv_toep_run(ConvArgs& a, int dtype, hipStream_t s);         // conv_toep.hip: <= 4 output channels as a Toeplitz product
+bool conv_toep_takes(const ConvArgs& a, int dtype);
+bool heads_dgrad_mfma_applicable(const uegan_conv_desc* d);      // heads_mfma.hip: one-channel heads' data gradient over the padded grid on the MFMA
+int heads_dgrad_mfma(const uegan_conv_desc* d, const void* dz, const void* w_ohwi, void* out, hipStream_t s);
+int conv_wide_run(ConvArgs& a, int dtype, hipStream_t s, bool interior = false);      // conv_wide.hip: 256-channel tiles, one wave per SIMD
+int conv_tall_run(ConvArgs& a, int dtype, hipStream_t s, bool interior = false);      // conv_wide.hip: 64- / 128-channel blocks on 16 x 32-pixel tiles, one wave per SIMD
+int conv_interior_run(ConvArgs& a, int dtype, hipStream_t s);    // conv_wide.hip: the image-free interior of a reflection-padded data gradient on those two
+int conv_s2fwd_run(ConvArgs& a, int dtype, hipStream_t s);       // conv_s2.hip: stride-2 forwards by input parity classes
+bool conv_flat_applicable(const uegan_conv_desc* d);             // conv_flat.hip: stride-2 data gradients over the padded grid, all parity classes in one launch
+int conv_flat_run(const uegan_conv_desc* d, const void* dz, const void* w_ihwo, const float* scale, void* out, hipStream_t s);
+// conv_stream.hip: the mirrored images of a reflection-padded data gradient behind the streaming kernel (rows_only: it added the x-mirrored ones itself)
+int launch_dgrad_images(ConvArgs& a, int dtype, hipStream_t s, bool rows_only);
 
 }  // namespace uegan

@@ -1,5 +1,6 @@
 // Streaming convolution kernel for the thin full-resolution layers (bf16, stride 1 or forward stride 2, <= 64 input and <= 64 output
-// channels: enc1, dec4, dec5, GAM-1, the 7x7 heads and their data gradients).  Included by conv.hip only.
+// channels: enc1, dec4, dec5, GAM-1, the 7x7 heads and their data gradients): the kernel template and the plan of a launch.  The plain
+// instantiations, the planner and the launcher are in conv_stream.hip, the hi + lo pair / epilogue-extra instantiations in conv_stream_ex.hip.
 //
 // These layers move hundreds of MB through a few GFLOP: they are bound by HBM and by launch-to-launch latency, not by
 // MFMA.  The tile-per-block kernels above re-stage the weights for every tile and expose the load latency of every tile.
@@ -13,8 +14,13 @@
 //   * output: D rows = output channels (4 consecutive per lane), columns = the 16 pixels of one tile row
 // Forward (either padding) handles image borders itself (reflected / zero-filled patch loads).  The data gradient of a
 // reflection-padded convolution is computed as the plain flipped-tap correlation with zero fill (every pixel's direct image); the
-// mirrored images of the pixels within `pad` of a border are added by dgrad_images_kernel (conv.hip) afterwards.
+// mirrored images of the pixels within `pad` of a border are added by dgrad_images_kernel (conv_stream.hip) afterwards.
 #pragma once
+#include "conv_core.h"
+
+#include <type_traits>
+
+namespace uegan {
 
 struct ConvStreamArgs {
   ConvArgs c;                 // geometry, tensors, epilogue
@@ -615,8 +621,6 @@ __global__ void __launch_bounds__(64 * NW, (LC >= 2 ? 1 : (LC == 1 ? 2 : 3)) * N
 }
 
 // ---- host side ----
-static bool g_use_stream = true;
-
 struct ConvStreamPlan {
   ConvStreamArgs a;
   int tn, pf, blocks;
@@ -631,196 +635,15 @@ struct ConvStreamPlan {
 bool conv_stream_launch_ex(const ConvStreamPlan& p, hipStream_t s);
 bool conv_stream_ex_available(const ConvStreamPlan& p);
 
-#ifndef UEGAN_CONV_STREAM_KERNEL_ONLY      // (conv_stream_ex.hip wants the kernel template and the plan struct only)
-static bool conv_stream_plan(const ConvArgs& c, int dtype, ConvStreamPlan& p, int max_pf = 4) {
-  const ConvGeom& g = c.g;
-  if (!g_use_stream || dtype != UEGAN_BF16 || g.KH != g.KW || !(g.KH & 1) || g.pad != (g.KH - 1) / 2) return false;
-  // hi + lo pairs / epilogue extras (uegan_conv2d_fwd_ex): plain stride-1 forwards, weights always as a pair when anything is
-  int pr = 0;
-  if (c.w_lo) pr = (c.in1_lo && g.C2 == 0) ? 2 : ((c.in2_lo && !c.in1_lo && g.C1 == 32 && g.C2 == 32) ? 3 : ((c.in1_lo || c.in2_lo) ? -1 : 1));
-  else if (c.in1_lo || c.in2_lo) pr = -1;
-  const int epx = c.mul ? 2 : (c.out_lo ? 1 : 0);
-  if (c.mul && c.out_lo) return false;                                      // (no instantiation writes both)
-  if (pr >= 2 && !epx) return false;                                        // (the source-pair instantiations all carry an epilogue extra)
-  if (pr < 0 || ((pr || epx) && (g.mode != 0 || g.stride != 1 || c.mask || c.out2))) return false;
-  if (pr >= 2 && g.pad_mode != UEGAN_PAD_REFLECT && g.pad != 0) return false;      // (the zero-filling staging path knows no lo plane)
-  if (c.mul && !c.out_mul) return false;
-  p.pr = pr; p.epx = epx;
-  const int sx = g.stride;
-  const bool cls = sx == 2 && g.mode == 1;      // data gradient of a stride-2 conv: four parity classes per tile
-  if (cls) {
-    if (!(g.C == 32 || g.C == 64) || g.OH != 2 * g.IH || g.OW != 2 * g.IW || g.pad_mode != UEGAN_PAD_REFLECT || g.C2 != 0) return false;
-  } else if (sx == 2) {
-    if (g.mode != 0 || g.OH != (g.IH + 2 * g.pad - g.KH) / 2 + 1 || g.OW != (g.IW + 2 * g.pad - g.KW) / 2 + 1) return false;
-  } else if (sx != 1 || g.IH != g.OH || g.IW != g.OW) {
-    return false;
-  }
-  if (!(g.C == 8 || g.C == 16 || g.C == 32 || g.C == 64) || c.N > 64 || c.N % 8 || (c.out2 && c.n_out1 % 8)) return false;
-  if (g.C1 % 8 || g.C2 % 8) return false;
-  if ((cls ? g.IH : g.OH) < 16 || (cls ? g.IW : g.OW) < 32) return false;
-  ConvStreamArgs& a = p.a;
-  a.c = c;
-  a.abl = UEGAN_ABL_BITS(g_abl_stream);
-  a.sx = cls ? 1 : sx;
-  a.cls = cls ? 1 : 0;
-  a.flip = g.mode == 1;
-  a.org = g.mode == 1 ? g.pad - (g.KH - 1) : -g.pad;
-  a.zero_fill = (g.mode == 1 || g.pad_mode != UEGAN_PAD_REFLECT) ? 1 : 0;
-  a.taps = g.KH * g.KW;
-  a.Clog = g.C == 8 ? 3 : (g.C == 16 ? 4 : (g.C == 32 ? 5 : 6));
-  a.rb = g.C * 2;
-  a.rblog = a.Clog + 1;
-  a.ksteps = (a.taps * g.C + 31) / 32;
-  a.KWmagic = 65536 / g.KW + 1;
-  for (int tap = 0; tap < a.taps; ++tap)
-    if (((tap * a.KWmagic) >> 16) != tap / g.KW) return false;
-  a.wrow = a.ksteps * 64;
-  // rows 64 B apart modulo the 256-byte bank row: conflict-free A reads (192 = -64 serves as well -- slot 12 n mod 16 is the same permutation of n & 3 --
-  // and is what lets dec4's weight PAIR fit the LDS beside its patches; the plain launches keep the layout they were measured with)
-  while (a.wrow % 256 != 64 && !(pr && a.wrow % 256 == 192)) a.wrow += 64;
-  p.tn = c.N <= 16 ? 1 : (c.N <= 32 ? 2 : 4);
-  a.wrows = (c.N + 7) / 8 * 8;
-  if (a.wrows > p.tn * 16) a.wrows = p.tn * 16;
-  a.wbytes = (a.wrows * a.wrow + 15) / 16 * 16;
-  a.wlo_off = a.wbytes;
-  if (pr) a.wbytes *= 2;                                             // (the lo part of the weights behind the hi matrix)
-  a.tbytes = a.ksteps * 256 + (a.ksteps * 4 + 255) / 256 * 256;      // lane offsets + weight-slice offsets per K step
-  // reflection-padded stride-1 data gradient on a map whose width is whole tiles: x-mirrored images inside the kernel (two more tables)
-  a.xmir = (!cls && g.mode == 1 && g.pad_mode == UEGAN_PAD_REFLECT && g.pad > 0 && g.pad < 8 && g.OW % 16 == 0 && g.KW == 2 * g.pad + 1) ? 1 : 0;
-  a.mtab_off = a.tbytes;
-  if (a.xmir) a.tbytes += 2 * a.ksteps * 256 + (2 * a.ksteps * 4 + 255) / 256 * 256;
-  if (pr && (a.xmir || cls)) return false;
-  a.tlo_off = a.tbytes;
-  if (pr == 3) a.tbytes += a.taps * 256;                             // the lo plane's per-tap lane offsets
-  a.c_lo = pr == 2 ? g.C : (pr == 3 ? g.C2 : 0);
-  a.rb_lo = a.c_lo * 2;
-  a.rblog_lo = a.c_lo == 8 ? 4 : (a.c_lo == 16 ? 5 : (a.c_lo == 32 ? 6 : 7));
-  a.lo_xoff = 0;
-  a.PW = sx * 15 + g.KW;
-  a.ymin = 0;
-  int cspan = 0;
-  for (int c = 0; c < 5; ++c) a.kstart[c] = 0;
-  if (cls) {
-    // source = i + (py + pad - t) / 2 over the taps t of class py: from (py - pad)/2 (t = K-1) up to (py + pad - t0)/2
-    const int ymin = (g.pad & 1) ? (1 - g.pad) / 2 : -(g.pad / 2);
-    int ymax = 0;
-    for (int py = 0; py < 2; ++py) {
-      const int t0 = (py + g.pad) & 1, v = (py + g.pad - t0) / 2;
-      if (v > ymax) ymax = v;
-    }
-    a.ymin = ymin;
-    cspan = ymax - ymin;
-    a.PW = 16 + cspan;
-    const int spt = g.C / 32;
-    for (int c = 0; c < 4; ++c) {
-      const int py = c >> 1, px = c & 1;
-      const int nty = (g.KH - ((py + g.pad) & 1) + 1) / 2, ntx = (g.KW - ((px + g.pad) & 1) + 1) / 2;
-      a.kstart[c + 1] = a.kstart[c] + nty * ntx * spt;
-    }
-    if (a.kstart[4] != a.ksteps) return false;
-  }
-  a.PWmagic = 65536 / a.PW + 1;
-  p.pf = 0;
-  p.lc = 1;
-  for (int pass = 1; pass < (pr == 3 ? 4 : 3) && !p.pf; ++pass) {      // 80 KB (two blocks per CU) if it fits, else 152 KB (PR 3: else all 160)
-    const int kb = CS_LDS_KB[pass], maxix = pass >= 2 ? 16 : 10;
-    for (int pf : {4, 2}) {
-      if (pf > max_pf) continue;
-      const int th = 4 * pf, ph = cls ? th + cspan : sx * (th - 1) + g.KH;
-      // (PR >= 2: both planes packed exactly, lanes without a chunk masked; else whole staging rounds: every lane of a round writes)
-      const int xbh = pr >= 2 ? ph * a.PW * a.rb : (ph * a.PW * a.rb + 4095) / 4096 * 4096;
-      const int xb = xbh + (pr >= 2 ? ph * a.PW * a.rb_lo : 0);
-      if (a.wbytes + a.tbytes + 2 * xb > kb * 1024 || (xb + 4095) / 4096 > maxix) continue;
-      bool ok = true;
-      for (int r = 0; r < ph * a.PW && ok; ++r) ok = ((r * a.PWmagic) >> 16) == r / a.PW;
-      if (!ok) continue;
-      p.pf = pf; a.TH = th; a.PH = ph; a.xbytes = xb; p.lc = pass;
-      if (pr >= 2) a.lo_xoff = xbh;
-      break;
-    }
-  }
-  if (!p.pf) return false;
-  p.nw = 4;
-  if (p.pf == 4 && (!cls || p.lc == 2) && p.lc == 2 && p.tn <= 2 && !a.xmir && !pr) {
-    // the same 16-row tile on 8 waves of 2 rows each (staging rounds of 512 lanes)
-    const int xb8 = (a.PH * a.PW * a.rb + 8191) / 8192 * 8192;
-    if (a.wbytes + a.tbytes + 2 * xb8 <= CS_LDS_KB[p.lc] * 1024 && xb8 / 8192 <= (p.lc == 2 ? 8 : 5)) { p.nw = 8; p.pf = 2; a.xbytes = xb8; }
-  }
-  // pairs on one block per CU: 8 waves as well (the same tile, half the rows per wave; the planes are packed exactly, so only the round count changes):
-  // dec5.0 0.96 -> 0.74 ms, dec4 2.09 -> 1.51 ms per 32 images
-  if (pr >= 2 && p.lc >= 2 && p.tn <= 2 && (a.xbytes + 8191) / 8192 <= 8) { p.nw = 8; p.pf /= 2; }
-  // one block per CU only pays for the thin layers: with 64 output channels (VGG conv1_2) or four parity classes per tile the
-  // patch kernel measured faster
-  if (p.lc == 2 && ((p.tn == 4 && sx == 1) || (cls && p.nw != 8))) return false;
-  // Every tile of the map.  The data gradient of a reflection-padded conv is computed as if the padding were zeros (the direct
-  // image of every pixel); the few pixels within `pad` of a border that also receive MIRRORED images get those added afterwards
-  // by dgrad_images_kernel (conv.hip) -- 0.8 % of a 512^2 map for pad 1, instead of a second MFMA launch over every border tile.
-  p.fixup = g.mode == 1 && g.pad_mode == UEGAN_PAD_REFLECT && g.pad > 0;
-  if (p.fixup && (g.OH <= 2 * g.pad + 2 || g.OW <= 2 * g.pad + 2)) return false;
-  a.ty0 = 0; a.tx0 = 0;
-  a.ty1 = ((cls ? g.IH : g.OH) + a.TH - 1) / a.TH;
-  a.tx1 = ((cls ? g.IW : g.OW) + 15) / 16;
-  a.tiles_total = g.B * (a.ty1 - a.ty0) * (a.tx1 - a.tx0);
-  const int maxb = p.lc == 2 ? 256 : 512;
-  int blocks = a.tiles_total < maxb ? a.tiles_total : maxb;
-  a.tiles_per_block = (a.tiles_total + blocks - 1) / blocks;
-  p.blocks = (a.tiles_total + a.tiles_per_block - 1) / a.tiles_per_block;
-  if ((pr || epx) && !conv_stream_ex_available(p)) return false;      // (a handful of instantiations: the generator's full-resolution layers)
-  return true;
-}
+// conv_stream.hip: does the streaming kernel take this problem, and how (false: not taken); run a plan; the profiler's scope around a launch
+// (mode: the kernel name's MODE field -- the gather mode, or 8 + PR for uegan_conv2d_fwd_ex)
+bool conv_stream_plan(const ConvArgs& c, int dtype, ConvStreamPlan& p, int max_pf = 4);
+void conv_stream_launch(const ConvStreamPlan& p, hipStream_t s);
+ProfScope conv_stream_prof(const ConvStreamPlan& p, int mode, hipStream_t s);
+// the STATS instantiations: can this plan carry the moments, the partials' workspace, arming the plan before its launch, the fold behind it
+bool conv_stream_stats_ok(const ConvStreamPlan& p);
+size_t conv_stream_stats_bytes(const ConvStreamPlan& p);
+void conv_stream_stats_arm(ConvStreamPlan& p, void* workspace);
+int conv_stream_stats_finalize(const ConvStreamPlan& p, float* mean, float* rstd, float eps, hipStream_t s);
 
-template <int TN, int PF>
-static void conv_stream_launch2(const ConvStreamPlan& p, hipStream_t s) {
-  const int blocks = p.blocks;
-  if (p.a.cls) {        // parity-class data gradient: own instantiation, so the plain kernel keeps its straight-line K loop
-    if constexpr (PF == 2 && TN <= 2) {
-      if (p.nw == 8) {
-        hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 2, true, false, 8>), dim3(blocks), dim3(512), 0, s, p.a);
-        return;
-      }
-    }
-    if (p.lc == 2) hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 2, true>), dim3(blocks), dim3(256), 0, s, p.a);
-    else hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, true>), dim3(blocks), dim3(256), 0, s, p.a);
-    return;
-  }
-  if constexpr (PF == 2 && TN <= 2) {
-    if (p.nw == 8) {
-      if (p.a.xmir) hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, false, true, 8>), dim3(blocks), dim3(512), 0, s, p.a);
-      else if (p.lc == 2) hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 2, false, false, 8>), dim3(blocks), dim3(512), 0, s, p.a);
-      else hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, false, false, 8>), dim3(blocks), dim3(512), 0, s, p.a);
-      return;
-    }
-  }
-  if (p.stats) {        // (forward with per-channel sums; conv_stream_stats_ok: 4 waves, 80-KB class, no mirrors, >= 32 output channels)
-    if constexpr (TN >= 2) {
-      hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, false, false, 4, true>), dim3(blocks), dim3(256), 0, s, p.a);
-      return;
-    }
-  }
-  if (p.a.xmir) {       // (own instantiation: the forward kernels keep their register budget)
-    if (p.lc == 2) hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 2, false, true>), dim3(blocks), dim3(256), 0, s, p.a);
-    else hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, false, true>), dim3(blocks), dim3(256), 0, s, p.a);
-    return;
-  }
-  if (p.lc == 2) hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 2, false>), dim3(blocks), dim3(256), 0, s, p.a);
-  else hipLaunchKernelGGL((conv_stream_kernel<TN, PF, 1, false>), dim3(blocks), dim3(256), 0, s, p.a);
-}
-// can this planned launch carry the per-channel sums?  (a block's tile range must span at most two images)
-static bool conv_stream_stats_ok(const ConvStreamPlan& p) {
-  const ConvGeom& g = p.a.c.g;
-  const int tpi = (p.a.ty1 - p.a.ty0) * (p.a.tx1 - p.a.tx0);
-  return g.mode == 0 && !p.a.cls && !p.a.xmir && p.nw == 4 && p.lc == 1 && !p.a.c.out2 && !p.a.c.mask && p.a.tiles_per_block <= tpi && p.tn >= 2;
-}
-static void conv_stream_launch(const ConvStreamPlan& p, hipStream_t s) {
-  if (p.pr || p.epx) {
-    (void)conv_stream_launch_ex(p, s);      // (the planner's caller checked conv_stream_ex_available)
-    return;
-  }
-  if (p.tn == 1 && p.pf == 4) conv_stream_launch2<1, 4>(p, s);
-  else if (p.tn == 1) conv_stream_launch2<1, 2>(p, s);
-  else if (p.tn == 2 && p.pf == 4) conv_stream_launch2<2, 4>(p, s);
-  else if (p.tn == 2) conv_stream_launch2<2, 2>(p, s);
-  else if (p.pf == 4) conv_stream_launch2<4, 4>(p, s);
-  else conv_stream_launch2<4, 2>(p, s);
-}
-#endif
+}  // namespace uegan

@@ -1,15 +1,10 @@
 // The streaming convolution kernel's instantiations with hi + lo PAIRS of 16-bit planes and / or epilogue extras (uegan_conv2d_fwd_ex, round 6):
 // the generator's full-resolution layers in the `precise` mode (enc1, ga1, dec4, dec5.0: operands and results carry ~2 x the significant bits of the
 // storage format) and dec4's forward with `y4.mul(x1)` (models.py:69) formed in its epilogue.  A translation unit of its own: the
-// plain instantiations in conv.hip keep their compile time and register budgets.
-#include "conv_core.h"
-
-#include <type_traits>
+// plain instantiations in conv_stream.hip keep their compile time and register budgets.
+#include "conv_stream.h"
 
 namespace uegan {
-
-#define UEGAN_CONV_STREAM_KERNEL_ONLY
-#include "conv_stream.h"
 
 namespace {
 // (TN, PF, LDS class, waves, STATS, PR, EPX) of the instantiations below

@@ -1,22 +1,10 @@
-// Spectral-norm power iteration / gradient, fused multi-tensor Adam, and the library's error plumbing.
+// Spectral-norm power iteration / gradient, and the fused multi-tensor Adam.
 // Reference arithmetic: torch.nn.utils.spectral_norm (models.py:185-188): 1 power iteration per training
 // forward, eps 1e-12, sigma = u^T W v, weight = weight_orig / sigma, u/v constants in backward;
 // torch.optim.Adam with weight_decay (L2 added to the gradient), trainer.py:337-338.
 #include "common.h"
 
-#include <stdarg.h>
-#include <stdio.h>
-
 namespace uegan {
-
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
 
 // <a, b>: one partial per block (<= SN_DOTB blocks: 64 made the largest layers' dot 2.5x slower than the atomic version); the consumers
 // add the partials in a fixed order (dot_fold) -- deterministic, where one float atomicAdd per block depended on the order the blocks
@@ -194,9 +182,6 @@ __global__ void rmsprop_kernel(const uegan_adam_tensor* desc, float lr, float al
 }  // namespace uegan
 
 using namespace uegan;
-
-extern "C" int uegan_version(void) { return UEGAN_VERSION; }
-extern "C" const char* uegan_last_error(void) { return g_err; }
 
 extern "C" int uegan_specnorm_grad(const float* g, const float* w, const float* u, const float* v, const float* sigma, float* dw, int rows,
                                    int cols, float* tmp, uegan_stream_t stream) {

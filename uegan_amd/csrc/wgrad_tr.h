@@ -1,4 +1,4 @@
-// Weight-gradient kernel for bf16 built on the gfx950 LDS transpose read (ds_read_b64_tr_b16).  Included by conv.hip only.
+// Weight-gradient kernel for bf16 built on the gfx950 LDS transpose read (ds_read_b64_tr_b16).  Included by wgrad.hip only.
 //
 //   dW[n][tap][c] = sum_pixels dz[pixel][n] * x[pixel*stride + tap - pad][c]          (reference: autograd of F.conv2d)
 //
@@ -454,8 +454,6 @@ __global__ void __launch_bounds__(256, BIG ? 1 : 2) wgrad_tr_kernel(WgradTrArgs 
 }
 
 // ---- host side: plan + launch ----
-static bool g_use_wgtr = true;
-
 struct WgradTrPlan {
   WgradTrArgs a;
   dim3 grid;
@@ -467,10 +465,9 @@ struct WgradTrPlan {
 static bool wgtr_ch_ok(int c) { return c == 8 || c == 16 || c == 32 || (c >= 64 && c % 64 == 0); }
 
 static bool wgtr_plan(const uegan_conv_desc* d, const ConvGeom& g, WgradTrPlan& p) {
-  if (!g_use_wgtr || d->dtype != UEGAN_BF16) return false;
+  if (!g_impl.wgtr || d->dtype != UEGAN_BF16) return false;
   const int C = d->C1 + d->C2, zC = d->Cout;
   if (!wgtr_ch_ok(C) || !wgtr_ch_ok(zC)) return false;
-  if (C < 64 && d->C2 != 0) { /* fine: sources are selected per 8-channel chunk */ }
   WgradTrArgs& a = p.a;
   a.g = g;
   a.abl = UEGAN_ABL_BITS(g_abl_stream);
