@@ -1,7 +1,11 @@
 """Kernel-level parity: every C-ABI op (through the autograd wrappers in uegan_amd/ops.py) against plain PyTorch fp32 /
 the CPU oracle on identical seeded inputs.  Each test runs on the CPU fiber emulator (`-m "not gpu"`) and on the
 MI355X (`-m gpu`).  Tolerances: fp32 path 2e-5 relative-to-max (accumulation order only); bf16 storage 2e-2
-against a reference evaluated on bf16-rounded operands."""
+against a reference evaluated on bf16-rounded operands.
+
+This file owns the convolution routes, the layout / resampling / normalisation ops and the small-size oracle checks of the losses,
+spectral norm and Adam.  The loss, spectral-norm, `sn_act_bwd` / `sn_grad_finish` and optimizer kernels in every launch regime
+(multi-block folds, block caps, grid-stride loops, 16-bit head maps) are tests/test_loss_optim_kernels.py's, against fp64 references."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -652,8 +652,9 @@ __device__ __forceinline__ float pred_term_grad(float p, int fid, float t) {
   switch (fid) {
     case UEGAN_PRED_BCE: return 1.f / (1.f + expf(-p)) - t;
     case UEGAN_PRED_LS: return 2.f * (p - t);
-    case UEGAN_PRED_HINGE_REAL: return p - 1.f < 0.f ? -1.f : 0.f;
-    case UEGAN_PRED_HINGE_FAKE: return -p - 1.f < 0.f ? 1.f : 0.f;
+    // torch.min(x, 0) hands half of the gradient to each argument where the two are equal (p exactly on the threshold)
+    case UEGAN_PRED_HINGE_REAL: return p - 1.f < 0.f ? -1.f : (p - 1.f == 0.f ? -0.5f : 0.f);
+    case UEGAN_PRED_HINGE_FAKE: return -p - 1.f < 0.f ? 1.f : (-p - 1.f == 0.f ? 0.5f : 0.f);
     case UEGAN_PRED_NEG_MEAN: return -1.f;
     default: return 1.f;
   }
