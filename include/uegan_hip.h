@@ -345,6 +345,10 @@ int uegan_copy_images(float* dst, const float* src_a, const float* src_b, const 
 /* [-1,1] NCHW fp32 -> uint8 NHWC exactly as tester.py:70-71 writes a PNG: denorm (utils.py:128-130: (x+1)/2 clamped to [0,1]),
  * then torchvision save_image's mul(255).add(0.5).clamp(0,255).to(uint8). */
 int uegan_quantize_u8(const float* x_nchw, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream);
+/* n (1..4) such images of equal shape side by side in ONE uint8 NHWC image y[B][H][n*W][C], image k in columns [k*W, (k+1)*W): the file
+ * save_image(torch.cat([denorm(a), denorm(b), ...], 3)) writes for samples, validation and test montages (trainer.py:182-183,244-245,
+ * tester.py:73-74), with uegan_quantize_u8's arithmetic.  srcs_nchw is a HOST array of n device pointers (passed to the kernel by value). */
+int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream);
 /* Per image b < B of two uint8 NHWC stacks, after cropping crop_border pixels on every side (CalcPSNR.py:24,56 / CalcSSIM.py:24,56):
  *   sqdiff_sum[b] (may be NULL) = sum (a - b)^2               -> PSNR = 10 log10(255^2 / (sqdiff_sum / n)), CalcPSNR.py:85-92
  *   ssim_sum[b]   (may be NULL) = sum over channels and valid 7x7 windows of the SSIM index with skimage's defaults as called at

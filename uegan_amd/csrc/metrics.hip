@@ -43,6 +43,67 @@ __global__ void quantize_u8_kernel(const float* x, uint8_t* y, int B, int C, int
   }
 }
 
+// ---- up to four [-1,1] NCHW fp32 images side by side -> ONE uint8 NHWC image [B][H][n*W][C], panel k in columns [k*W, (k+1)*W): what
+// save_image(torch.cat([denorm(a), denorm(b), ...], 3)) writes (trainer.py:182-183,244-245, tester.py:73-74), with quantize_u8_kernel's
+// arithmetic.  The source pointers travel by value, like CopyTable.  HBM-bound: 4 B read + 1 B written per element, each exactly once. ----
+constexpr int MONTAGE_MAX_SRCS = 4;
+constexpr int MONTAGE_THREADS = 256;
+constexpr int MONTAGE_MAX_BLOCKS = 1024;      // grid cap: 4 blocks (16 waves) per CU on 256 CUs, the rest by grid stride
+constexpr int MONTAGE_VEC = 4;                // pixels per thread of the vector path (uegan_amd/tester.py mirrors these three numbers)
+struct MontageSrcs {
+  const float* p[MONTAGE_MAX_SRCS];
+};
+
+__device__ __forceinline__ uint32_t quantize_u8(float x) {
+  float v = (x + 1.f) / 2.f;
+  v = fminf(fmaxf(v, 0.f), 1.f);
+  v = v * 255.f + 0.5f;
+  v = fminf(fmaxf(v, 0.f), 255.f);
+  return (uint32_t)(uint8_t)v;                 // truncation, like Tensor.to(torch.uint8)
+}
+
+// vector path (W % 4 == 0, sources 16-byte and y 4-byte aligned): one thread = 4 neighbouring pixels of one panel row: one 16-byte load per
+// plane (a wave reads 1 KiB of a plane row in one instruction), C whole dwords stored (4 * C bytes: the 4 pixels' bytes are contiguous in NHWC)
+template <int C>
+__global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int H, int W) {
+  const int wq = W / MONTAGE_VEC;
+  const size_t items = rows * n * wq;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
+    const int q = (int)(i % wq);
+    const size_t t = i / wq;
+    const int k = (int)(t % n);
+    const size_t row = t / n;                  // b * H + h
+    const size_t b = row / H, h = row - b * H;
+    const float* src = s.p[k] + ((b * C) * H + h) * W + (size_t)q * MONTAGE_VEC;
+    uint32_t by[MONTAGE_VEC * C];              // byte j of the 4 * C output bytes = pixel j / C, channel j % C
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * H * W);
+      by[0 * C + c] = quantize_u8(v[0]);
+      by[1 * C + c] = quantize_u8(v[1]);
+      by[2 * C + c] = quantize_u8(v[2]);
+      by[3 * C + c] = quantize_u8(v[3]);
+    }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(y + ((row * n + k) * W + (size_t)q * MONTAGE_VEC) * C);
+#pragma unroll
+    for (int d = 0; d < C; ++d) dst[d] = by[4 * d] | (by[4 * d + 1] << 8) | (by[4 * d + 2] << 16) | (by[4 * d + 3] << 24);
+  }
+}
+
+// scalar path (any width, any alignment, any C): one thread = one output pixel
+__global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int C, int H, int W) {
+  const size_t items = rows * n * W;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W);
+    const size_t t = i / W;
+    const int k = (int)(t % n);
+    const size_t row = t / n;
+    const size_t b = row / H, h = row - b * H;
+    const float* src = s.p[k] + ((b * C) * H + h) * W + w;
+    for (int c = 0; c < C; ++c) y[i * C + c] = (uint8_t)quantize_u8(src[(size_t)c * H * W]);
+  }
+}
+
 // ---- sum of squared differences over the cropped region, per image (double accumulation; the terms are integers and the sums stay
 // below 2^53, so the double atomicAdd per block is exact and the result does not depend on the order of the blocks) ----
 __global__ void sqdiff_u8_kernel(const uint8_t* a, const uint8_t* b, double* out, int H, int W, int C, int crop) {
@@ -216,6 +277,31 @@ extern "C" int uegan_quantize_u8(const float* x_nchw, uint8_t* y_nhwc, int B, in
   const size_t n = (size_t)B * C * H * W;
   const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   hipLaunchKernelGGL(quantize_u8_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_nchw, y_nhwc, B, C, H * W);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(srcs_nchw && y_nhwc && B > 0 && C > 0 && H > 0 && W > 0, "bad montage_u8 args");
+  UEGAN_CHECK_ARG(n >= 1 && n <= MONTAGE_MAX_SRCS, "montage_u8 takes 1..%d images (got %d)", MONTAGE_MAX_SRCS, n);
+  MontageSrcs s;
+  bool vec = W % MONTAGE_VEC == 0 && (uintptr_t)y_nhwc % 4 == 0 && (C == 1 || C == 3 || C == 4);
+  for (int k = 0; k < MONTAGE_MAX_SRCS; ++k) {
+    s.p[k] = k < n ? srcs_nchw[k] : nullptr;
+    if (k < n) {
+      UEGAN_CHECK_ARG(srcs_nchw[k], "montage_u8: null image %d", k);
+      vec = vec && (uintptr_t)srcs_nchw[k] % 16 == 0;
+    }
+  }
+  const size_t rows = (size_t)B * H;
+  const size_t items = rows * n * (vec ? W / MONTAGE_VEC : W);
+  const size_t want = (items + MONTAGE_THREADS - 1) / MONTAGE_THREADS;
+  const dim3 grid((unsigned)(want < (size_t)MONTAGE_MAX_BLOCKS ? want : (size_t)MONTAGE_MAX_BLOCKS)), block(MONTAGE_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+  if (!vec) hipLaunchKernelGGL(montage_u8_kernel, grid, block, 0, st, s, n, y_nhwc, rows, C, H, W);
+  else if (C == 3) hipLaunchKernelGGL((montage_u8_vec_kernel<3>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
+  else if (C == 1) hipLaunchKernelGGL((montage_u8_vec_kernel<1>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
+  else hipLaunchKernelGGL((montage_u8_vec_kernel<4>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }

@@ -3,6 +3,8 @@
     enhance(G, x)                     tester.py:58-67: `G.eval()`, `torch.no_grad()`, one `G(x)` per image
     GraphedGenerator(G, shape)        the same forward captured once into a hipGraph and replayed (batch-1 inference is
                                       ~60 dependent launches: launch latency, not arithmetic, sets its time)
+    montage_u8(a, b, ...)             `to_uint8_image(torch.cat([a, b, ...], 3))` in one launch: the side-by-side sample / compare images
+                                      (trainer.py:182-183,244-245, tester.py:73-74)
     to_uint8_image(x)                 what tester.py:70-71 writes to a PNG: denorm (utils.py:128-130) + torchvision save_image's
                                       mul(255).add(0.5).clamp(0,255).to(uint8), NHWC
     calculate_psnr / calculate_ssim   metrics/CalcPSNR.py:85-92 and metrics/CalcSSIM.py:63 (skimage defaults) with the 4-pixel
@@ -81,6 +83,32 @@ def to_uint8_image(x):
     return y
 
 
+# the launcher's constants (csrc/metrics.hip: MONTAGE_MAX_BLOCKS, MONTAGE_THREADS, MONTAGE_VEC): above MAX_BLOCKS * THREADS work items
+# (4 pixels each on the vector path, 1 on the scalar path) the kernels loop by grid stride -- tests/test_montage.py crosses both thresholds
+MONTAGE_MAX_BLOCKS, MONTAGE_THREADS, MONTAGE_VEC = 1024, 256, 4
+MONTAGE_MAX_IMAGES = 4
+
+
+def montage_u8(*images):
+    """1..4 float32 [B,C,H,W] images of equal shape -> uint8 [B,H,n*W,C], image k in columns [k*W, (k+1)*W): bit for bit
+    `to_uint8_image(torch.cat(images, 3))`, i.e. what `save_image(torch.cat([denorm(a), denorm(b), ...], 3))` writes for the sample and
+    compare montages (trainer.py:182-183,244-245, tester.py:73-74), in one launch that reads every source once (uegan_montage_u8)."""
+    n = len(images)
+    if not 1 <= n <= MONTAGE_MAX_IMAGES:
+        raise ValueError("montage_u8 takes 1..%d images (got %d)" % (MONTAGE_MAX_IMAGES, n))
+    for x in images:
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4:
+            raise TypeError("montage_u8 expects float32 [B,C,H,W] tensors")
+        if x.shape != images[0].shape or x.device != images[0].device:
+            raise ValueError("montage_u8: the images must have one shape and one device (got %s and %s)" % (tuple(images[0].shape), tuple(x.shape)))
+    xs = [x.detach().contiguous() for x in images]
+    B, C, H, W = xs[0].shape
+    y = torch.empty((B, H, n * W, C), dtype=torch.uint8, device=xs[0].device)
+    ops._chk(y, *xs)
+    L.check(ops.lib().uegan_montage_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, H, W, ops._stream()))
+    return y
+
+
 def _as_stack(img):
     if img.dtype != torch.uint8:
         raise TypeError("metrics take uint8 HWC / BHWC images (to_uint8_image)")
@@ -124,9 +152,10 @@ def mean_metric(values):
     return sum(values) / len(values)
 
 
-def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None):
+def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suffix="testFakeExp", compare_dir=None,
+             compare_suffix="testRealRaw_testFakeExp"):
     """Tester.test (tester.py:40-105) over a `uegan_amd.data` test loader: `G.eval()` forward per batch (:64-67), the enhanced image of
-    every sample as `<name>_<tag>_testFakeExp.png` in `save_dir` (:69-71: the 8-bit image torchvision's save_image writes; None: no
+    every sample as `<name>_<tag>_<suffix>.png` in `save_dir` (:69-71: the 8-bit image torchvision's save_image writes; None: no
     files), and -- what calc_psnr / calc_ssim then compute from those files against the label images (:96-103) -- PSNR and SSIM of
     each enhanced image against `img_exp`, here straight from the device tensors.  Returns {"names", "psnr", "ssim", "mean_psnr",
     "mean_ssim"} (true means).
@@ -134,8 +163,10 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None):
     Restriction: the label here is the loader's `img_exp` -- the label FILE resized to the test size by the loader's transform
     (data_loader.py:95-99) and re-quantised to 8 bits -- whereas calc_psnr / calc_ssim read the ORIGINAL files of test_label_dir.  The
     numbers agree with the reference's when the label files already have the test size (the reference itself needs equal shapes:
-    CalcPSNR.py:87 raises otherwise); for labels of another size decode them yourself and call calculate_psnr / calculate_ssim.  The
-    test_compare montage images (tester.py:73-90) are not written.
+    CalcPSNR.py:87 raises otherwise); for labels of another size decode them yourself and call calculate_psnr / calculate_ssim.
+
+    compare_dir: also write the raw image and the enhanced one side by side (tester.py:73-74; `montage_u8`) as
+    `<name>_<tag>_<compare_suffix>.png` there.  Validation passes suffix="valFakeExp", compare_suffix="valRealRaw_valFakeExp" (trainer.py:242,245).
 
     nima: a `uegan_amd.nima.NIMA` module -> also "nima" / "nima_std" (per image) and "mean_nima" (true mean): what calc_nima (tester.py:91-94,
     on by default in the reference: config.py:80) computes from the saved files, here from the same 8-bit images on the device.  It needs no
@@ -144,11 +175,13 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None):
     names, psnr, ssim, nima_mean, nima_std = [], [], [], [], []
     if nima is not None:
         from . import nima as nima_mod
-    if save_dir is not None:
-        os.makedirs(save_dir, exist_ok=True)
+    for d in (save_dir, compare_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
     for batch in loader:
         fake = enhance(G, batch.img_raw)
         q = to_uint8_image(fake)
+        pair = montage_u8(batch.img_raw, fake) if compare_dir is not None else None
         if metrics:
             ref = to_uint8_image(batch.img_exp)
             psnr += calculate_psnr(q, ref)
@@ -162,7 +195,12 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None):
             from PIL import Image
             host = q.cpu().numpy()
             for i, name in enumerate(batch.img_name):
-                Image.fromarray(host[i], "RGB").save(os.path.join(save_dir, "%s_%s_testFakeExp.png" % (name, tag)))
+                Image.fromarray(host[i], "RGB").save(os.path.join(save_dir, "%s_%s_%s.png" % (name, tag, suffix)))
+        if pair is not None:
+            from PIL import Image
+            host = pair.cpu().numpy()
+            for i, name in enumerate(batch.img_name):
+                Image.fromarray(host[i], "RGB").save(os.path.join(compare_dir, "%s_%s_%s.png" % (name, tag, compare_suffix)))
     out = {"names": names, "psnr": psnr, "ssim": ssim}
     if metrics and names:
         out["mean_psnr"], out["mean_ssim"] = mean_metric(psnr), mean_metric(ssim)

@@ -239,7 +239,8 @@ class LambdaLR:
 class Trainer:
     def __init__(self, G, D, percep=None, pool_size=50, g_lr=1e-4, d_lr=4e-4, beta1=0.5, beta2=0.999, lambda_adv=0.1, lambda_percep=1.0,
                  lambda_idt=0.1, adv_input=True, group=None, rng=random, broadcast_init=True, fused_passes=True, adv_loss_type="rahinge",
-                 optimizer_type="adam", alpha=0.9, defer_g_update=None, overlap=True, early_taps=False, loss_scale=None, early_sn=False):
+                 optimizer_type="adam", alpha=0.9, defer_g_update=None, overlap=True, early_taps=False, loss_scale=None, early_sn=False,
+                 idt_loss_type="l1"):
         """fused_passes: run the repeated network applications of a step as single batched passes (uegan_amd/fused.py: one
         generator pass for :85 + :112, one discriminator pass per optimizer step with the loss fused behind it, one VGG pass for
         both fidelity-loss images).  False: one module call per reference line, exactly as trainer.py:85-119 is written -- the
@@ -265,7 +266,7 @@ class Trainer:
         default_flags = getattr(G, "default_flags", True) and getattr(D, "default_flags", True) and adv_loss_type == "rahinge"
         self.fused_passes = fused_passes = fused_passes and default_flags
         self.criterionPercep = percep if percep is not None else PerceptualLoss().to(next(G.parameters()).device)
-        self.criterionIdt = MultiscaleRecLoss(scale=3, rec_loss_type="l1", multiscale=True)
+        self.criterionIdt = MultiscaleRecLoss(scale=3, rec_loss_type=idt_loss_type, multiscale=True)       # trainer.py:56
         self.criterionGAN = GANLoss(adv_loss_type)                                        # trainer.py:44
         self.lambda_adv, self.lambda_percep, self.lambda_idt, self.adv_input = lambda_adv, lambda_percep, lambda_idt, adv_input
         self.g_lr0, self.d_lr0 = g_lr, d_lr
