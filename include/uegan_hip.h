@@ -66,7 +66,8 @@ enum {
   UEGAN_TUNE_FWD_STATS = 10,    /* default 1: uegan_conv2d_fwd_stats lets the streaming kernel emit the per-channel moments; 0: it declines (plain forward, the caller's moments pass) */
   UEGAN_TUNE_WGRAD_XCD = 11,    /* default 1: wgrad_tr_kernel orders its blocks so that all blocks of one pixel split run behind one XCD's L2 (needs a split count that is a multiple of 8); 0: launch order */
   UEGAN_TUNE_VGG_EPI = 12,      /* default 1: uegan_conv2d_dgrad_act_tap / uegan_conv2d_dgrad_unpool fold the fidelity-loss tap gradient / the max-pool backward into the data gradient's epilogue where conv_tall_kernel takes the layer; 0: they decline (the caller's two passes) */
-  UEGAN_TUNE_COUNT = 13
+  UEGAN_TUNE_GAM_BWD = 13,      /* default 1: uegan_gam_bwd_ws_bytes offers the one-pass backward of the full-resolution attention modules (gam_bwd.hip); 0: it declines (the caller's separate InstanceNorm / data-gradient / weight-gradient / activation backward passes); n >= 2: as 1 with the persistent grid capped at n blocks (tests: multi-tile, image-crossing block ranges on small shapes) */
+  UEGAN_TUNE_COUNT = 14
 };
 int uegan_set_tuning(int knob, int value, int* previous);
 /* on-device check of the MFMA fragment layouts this library assumes (A=I, asymmetric B). 0 = ok. */
@@ -425,6 +426,21 @@ int uegan_instnorm_fwd(int dtype, const void* x, void* y, float* mean, float* rs
 /* dx = rstd * (dy - mean(dy) - y * mean(dy*y)); tmp = fp32 [uegan_reduce_workspace_floats] scratch */
 int uegan_instnorm_bwd(int dtype, const void* dy, const void* y, const float* rstd, void* dx, float* tmp, int B, int HW,
                        int C, uegan_stream_t stream);
+
+/* One-pass backward of an attention module y = IN(W x) on a full-resolution map, fused with the activation backward of x's producer
+ * (gam_bwd.hip).  g, y, x: [B][HW][C] in the 16-bit storage format; rstd: fp32 [B*C] (the forward's); w_ihwo: the packed IHWO copy of W that the
+ * 1x1 data gradient reads; add1 / add2: gradients of x's other consumers (x's shape; either may be NULL); act: x's activation, UEGAN_ACT_NONE
+ * or UEGAN_ACT_LRELU.
+ *   dz     = rstd (g - mean g - y mean(g y))   rounded to the storage format (what uegan_instnorm_bwd stores)
+ *   dz_enc = (add1 + add2 + W^T dz) act'(x)
+ *   dw     = sum_pixels dz x^T                 into columns [0, Cin_w = C) of the fp32 [C][Cin_row] matrix dw (accumulate != 0: added to it)
+ * Up to four launches on `stream`.  uegan_gam_bwd_ws_bytes: the workspace to bring, or 0 where the library declines (fp32 storage, C other than
+ * 32 / 64, another activation, UEGAN_TUNE_GAM_BWD = 0): ask at forward time and build the graph accordingly.  uegan_gam_bwd itself does not read
+ * the knob -- it plans its grid from the shape and the workspace size -- so a graph built on a non-zero answer always finishes. */
+size_t uegan_gam_bwd_ws_bytes(int dtype, int B, int HW, int C, int act);
+int uegan_gam_bwd(int dtype, const void* g, const void* y, const void* x, const float* rstd, const void* w_ihwo, const void* add1,
+                  const void* add2, int act, void* dz_enc, float* dw, int Cin_row, int Cin_w, int accumulate, void* workspace,
+                  size_t workspace_bytes, int B, int HW, int C, uegan_stream_t stream);
 
 /* The norm_fun / act_fun variants of ConvBlock (models.py:88-101, 249-281): BatchNorm2d / InstanceNorm2d(affine=True,
  * track_running_stats=True) followed by LeakyReLU(0.2) | ReLU | Swish | SELU, as an affine map with explicit per-(b,c) coefficients

@@ -113,6 +113,8 @@ SIGNATURES = {
     "uegan_reduce_workspace_floats": (c_sz, [c_int, c_int, c_int]),
     "uegan_instnorm_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f32, c_vp]),
     "uegan_instnorm_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "uegan_gam_bwd_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    "uegan_gam_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_sz, c_int, c_int, c_int, c_vp]),
     "uegan_moments": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "uegan_affine_act_fwd": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "uegan_affine_act_bwd_sums": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),

@@ -229,6 +229,17 @@ __device__ __forceinline__ void wgtr_wait_loads() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
 }
+// The gfx950 LDS transpose read (ds_read_b64_tr_b16) of the weight-gradient kernels (wgrad_tr.h, gam_bwd.hip): within a 16-lane group, lane s
+// supplies the address of 4 consecutive 16-bit channels [4*(s&3), +4) of pixel (s>>2) and receives the 4 pixels of channel s.
+__device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
+  typedef short v4s_t __attribute__((ext_vector_type(4)));
+  const v4s_t r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)p);
+  return __builtin_bit_cast(u32x2, r);
+}
+// XOR term for the 16-byte chunk index of LDS row r (rb bytes per row) under which those reads hit distinct banks
+__device__ __forceinline__ int wgtr_swz(int rb, int r) {
+  return rb == 128 ? (r & 6) : (rb == 64 ? ((r >> 1) & 2) : 0);
+}
 
 // ----------------------------------------------------------------------------------------------------
 // Gather-GEMM kernel: out[pixel][n] = epi( sum_{image, tap, c} gather(pixel, tap, c) * w[n][tap][c] )

@@ -1045,17 +1045,28 @@ extern "C" int uegan_instnorm_apply_pair(int dtype, const void* x, const void* x
   return UEGAN_OK;
 }
 
+// the two sums of the InstanceNorm backward, {sum dy, sum dy*y} per (image, channel): tot[(b*C + c)*2 + {0,1}] inside tmp (gam_bwd.hip's first two launches too)
+int uegan::instnorm_bwd_sums(int dtype, const void* dy, const void* y, float* tmp, int B, int HW, int C, hipStream_t s, const float** tot_out) {
+  RedPlan p = make_plan(B, HW, C, epc_of(dtype));
+  dim3 grid(p.S, p.ncg, B);
+  float* tot = tmp + (size_t)B * p.S * C * 3;
+  DISPATCH_TV(dtype, p.V, hipLaunchKernelGGL((instnorm_bwd_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dy, (const T*)y, tmp, p));
+  UEGAN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sums_finalize_kernel, dim3(bc_blocks(p, 2)), dim3(256), 0, s, tmp, tot, p, 2);
+  UEGAN_CHECK_LAUNCH();
+  *tot_out = tot;
+  return UEGAN_OK;
+}
+
 extern "C" int uegan_instnorm_bwd(int dtype, const void* dy, const void* y, const float* rstd, void* dx, float* tmp, int B, int HW, int C,
                                   uegan_stream_t stream) {
   UEGAN_CHECK_ARG(dy && y && rstd && dx && tmp && B > 0 && HW > 0 && C > 0, "bad instnorm args");
   RedPlan p = make_plan(B, HW, C, epc_of(dtype));
   dim3 grid(p.S, p.ncg, B);
   hipStream_t s = (hipStream_t)stream;
-  float* tot = tmp + (size_t)B * p.S * C * 3;
-  DISPATCH_TV(dtype, p.V, hipLaunchKernelGGL((instnorm_bwd_partial_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dy, (const T*)y, tmp, p));
-  UEGAN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sums_finalize_kernel, dim3(bc_blocks(p, 2)), dim3(256), 0, s, tmp, tot, p, 2);
-  UEGAN_CHECK_LAUNCH();
+  const float* tot = nullptr;
+  const int rc = instnorm_bwd_sums(dtype, dy, y, tmp, B, HW, C, s, &tot);
+  if (rc) return rc;
   DISPATCH_TV(dtype, p.V, hipLaunchKernelGGL((instnorm_bwd_apply_kernel<T, V>), grid, dim3(256), 0, s, (const T*)dy, (const T*)y, rstd, tot, (T*)dx, p));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;

@@ -338,6 +338,14 @@ __global__ void wgrad_direct_kernel(WgradArgs a, float* dw, const float* scale_p
 
 using namespace uegan;
 
+int uegan::wgrad_reduce_1x1(const float* ws, float* dw, int nsplit, int N, int C, int Cin_w, int Cin_row, size_t pstride, int acc, hipStream_t s) {
+  const size_t total = (size_t)N * C;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, s, ws, dw, (float*)nullptr, (const float*)nullptr, nsplit, N, C,
+                     Cin_w, 1, 1, pstride, acc, 0, Cin_row);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
 // everything a weight-gradient launch needs, decided once: the size query and the launcher both read it from here
 struct WgradPlan {
   WgradArgs a;

@@ -53,21 +53,12 @@ struct WgradTrArgs {
                                     // built in LDS per tile (hE = KW*N rows, hEB = bytes per dzx pixel); slots = (ty, 16 channels)
 };
 
-__device__ __forceinline__ int wgtr_swz(int rb, int r) {   // XOR term for the 16-byte chunk index of LDS row r
-  return rb == 128 ? (r & 6) : (rb == 64 ? ((r >> 1) & 2) : 0);
-}
+// (wgtr_swz, lds_read_tr16: conv_core.h -- gam_bwd.hip takes its weight-gradient fragments the same way)
 
 template <int KB>
 __device__ __forceinline__ unsigned char* wgtr_lds() {
   __shared__ __attribute__((aligned(16))) unsigned char buf[KB * 1024];
   return buf;
-}
-
-// 4 consecutive bf16 per supplier lane -> 4 pixels of one channel per receiver lane (see header)
-__device__ __forceinline__ u32x2 lds_read_tr16(const unsigned char* p) {
-  typedef short v4s_t __attribute__((ext_vector_type(4)));
-  const v4s_t r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s_t*)p);
-  return __builtin_bit_cast(u32x2, r);
 }
 
 constexpr int WGTR_SMALL_KB = 80, WGTR_BIG_KB = 152;

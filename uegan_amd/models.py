@@ -90,8 +90,8 @@ class Conv2d(_InvalidatingModule):
             bound = 1 / math.sqrt(fan_in)
             nn.init.uniform_(self.bias, -bound, bound)
 
-    def forward(self, x, x2=None, n_out=1, ex=None):
-        return ops.conv2d(x, x2, self.weight, self.bias, self.cfg, n_out=n_out, ex=ex)
+    def forward(self, x, x2=None, n_out=1, ex=None, premasked=None):
+        return ops.conv2d(x, x2, self.weight, self.bias, self.cfg, n_out=n_out, ex=ex, premasked=premasked)
 
 
 class SpectralNormConv2d(_InvalidatingModule):
@@ -170,11 +170,13 @@ class ConvBlock(nn.Module):
         self.main = nn.Sequential(*mods)
         self.post = post
 
-    def forward(self, x, x2=None, n_out=1, ex=None):
-        y = self.main[1](x, x2, n_out=n_out, ex=ex)
+    def forward(self, x, x2=None, n_out=1, ex=None, premasked=None):
+        if premasked is not None and not isinstance(self.main[1], Conv2d):
+            raise RuntimeError("a per-call premasked is a feature of the plain single-kernel block")
+        y = self.main[1](x, x2, n_out=n_out, ex=ex) if premasked is None else self.main[1](x, x2, n_out=n_out, ex=ex, premasked=premasked)
         if self.post is None:
             return y
-        if n_out != 1 or ex is not None:
+        if n_out != 1 or ex is not None or premasked is not None:
             raise RuntimeError("output aliases / convolution extras are features of the single-kernel block")
         return self.post(y)
 
@@ -259,11 +261,23 @@ class GAM(nn.Module):
         else:
             y = ops.conv2d(x, None, fuse.weight, None, self._cfg, sn=sn, stats=holder)
             y = ops.instnorm(y, holder.value)
+        y = self._touch(y)
+        return y if x_lo is None else (y, y_lo)
+
+    def _touch(self, y):
         if torch.is_grad_enabled():
-            dead = [p for p in (self.conv[0].weight, self.conv[2].weight, fuse.bias) if p.requires_grad]
+            dead = [p for p in (self.conv[0].weight, self.conv[2].weight, self.fuse[0].bias) if p.requires_grad]
             if dead:
                 y = _TouchParams.apply(y, *dead)
-        return y if x_lo is None else (y, y_lo)
+        return y
+
+    def hub(self, x, x_act, n_x, wsb):
+        """x (the output of a convolution run with premasked=True whose activation was x_act) -> (x once per further consumer ..., ga(x)) as one graph
+        node whose backward is the one-pass kernel (ops.gam_hub; wsb: ops.gam_bwd_ws_bytes, non-zero); plain 16-bit storage, no spectral norm"""
+        if self.use_sn:
+            raise RuntimeError("GAM.hub: not with spectral norm")
+        outs = ops.gam_hub(x, self.fuse[0].weight, self._cfg, x_act, n_x, wsb)
+        return outs[:-1] + (self._touch(outs[-1]),)
 
 
 class Generator(_InvalidatingModule):
@@ -381,11 +395,25 @@ class Generator(_InvalidatingModule):
         # encoder activations with several consumers (next encoder stage, attention module, final modulation) come back as one
         # alias per consumer: their gradients meet inside the producing conv's activation-backward kernel (ops._ConvFn)
         ex1 = X(pair_w=True, dup_cin=True, want_lo=True) if P else None
-        x1a, x1b, x1c = self.enc1(xin, n_out=3, ex=ex1)
+        # the full-resolution attention modules ga1 / ga2 in the plain 16-bit modes: (encoder activation, module) is one graph node whose backward is one
+        # streaming kernel (ops.gam_hub: InstanceNorm backward, both 1x1 gradients and the encoder's activation backward) where the library offers it
+        B, H, W, _ = xin.shape
+        cd = self.enc1.main[1].out_channels
+        hub = (not P) and torch.is_grad_enabled()
+        wsb1 = ops.gam_bwd_ws_bytes(xin.dtype, B, H * W, cd, ops.ACT_LRELU) if hub else 0
+        wsb2 = ops.gam_bwd_ws_bytes(xin.dtype, B, (H // 2) * (W // 2), 2 * cd, ops.ACT_LRELU) if hub else 0
+        g1 = g2 = None
+        if wsb1:
+            x1a, x1c, g1 = self.ga1.hub(self.enc1(xin, premasked=True), ops.ACT_LRELU, 2, wsb1)
+        else:
+            x1a, x1b, x1c = self.enc1(xin, n_out=3, ex=ex1)
         x1_lo = ex1.y_lo if P else None
         # (precise: enc2's and upsample4's WEIGHTS as pairs too -- the two deep layers whose weight rounding, a systematic perturbation, carried the tail of
         # the pixel error in tools/diag_g_hilo.py; their sources and results stay plain)
-        x2a, x2b = self.enc2(x1a, n_out=2, ex=X(pair_w=True) if P else None)
+        if wsb2:
+            x2a, g2 = self.ga2.hub(self.enc2(x1a, premasked=True), ops.ACT_LRELU, 1, wsb2)
+        else:
+            x2a, x2b = self.enc2(x1a, n_out=2, ex=X(pair_w=True) if P else None)
         x3a, x3b = self.enc3(x2a, n_out=2)
         x4a, x4b = self.enc4(x3a, n_out=2)
         x5 = self.enc5(x4a)
@@ -393,14 +421,14 @@ class Generator(_InvalidatingModule):
 
         y1 = self.dec1(self._up(self.upsample1, x5), self.ga4(x4b))
         y2 = self.dec2(self._up(self.upsample2, y1), self.ga3(x3b))
-        y3 = self.dec3(self._up(self.upsample3, y2), self.ga2(x2b))
+        y3 = self.dec3(self._up(self.upsample3, y2), g2 if wsb2 else self.ga2(x2b))
         # y4.mul(x1) (models.py:69) is formed by dec4's epilogue from its fp32 result where a kernel does that (16-bit storage); `mul` then only records
         # the backward.  clamp(tanh(dec5.1) + x) likewise by dec5.1's epilogue (outs).
         if P:
             g1, g1_lo = self.ga1(x1b, x_lo=x1_lo)
             ex4 = X(x2_lo=g1_lo, pair_w=True, mul=x1c, mul_lo=x1_lo, want_mul_lo=True)
         else:
-            g1 = self.ga1(x1b)
+            g1 = g1 if wsb1 else self.ga1(x1b)
             ex4 = X(mul=x1c) if (xin.dtype != torch.float32 and ops.fuse_epilogues[0]) else None
         y4 = self.dec4(self._up(self.upsample4, y3, ex=X(pair_w=True) if P else None), g1, ex=ex4)
         prod = ops.mul(y4, x1c, act_a=ops.ACT_LRELU, given=ex4.prod if ex4 is not None else None)      # y4's LeakyReLU' applied in mul's backward

@@ -441,11 +441,34 @@ def _fwd_plain(d, x1, x2, ohwi, biasc, scale, y):
     L.check(lib().uegan_conv2d_fwd(C.byref(d), _p(x1), _p(x2), _p(ohwi), _p(biasc), _p(scale), _p(y), _stream()))
 
 
+def _wgrad_target(wsink, bsink, has_bias, want_w, sn, weight, cfg, n_bias, dev):
+    """where a layer's weight (and bias) gradient goes -> (sink, dw, db, acc): straight into the optimizer's flat bucket when both gradients live
+    there (acc: beta = 1 after the first touch; the spectral-norm correction works in place on ONE call's gradient, so it needs the first touch),
+    else into fresh tensors for autograd"""
+    sink = (wsink is not None and want_w and (not has_bias or (bsink is not None and bsink.dirty == wsink.dirty)) and (sn is None or not wsink.dirty))
+    if sink:
+        return True, wsink.view, (bsink.view if has_bias else None), (3 if wsink.dirty else 0)
+    # (a column-slice conv writes only its own columns: the rest of the gradient is zero)
+    dw = (torch.zeros if cfg.cin_used is not None else torch.empty)(weight.shape, dtype=torch.float32, device=dev)
+    db = torch.empty((n_bias,), dtype=torch.float32, device=dev) if has_bias else None
+    return False, dw, db, 0
+
+
+def _wgrad_done(sink, wsink, bsink, has_bias, dw, db):
+    """after the weight-gradient launch: what autograd gets (None where the gradient went into a sink, which is told)"""
+    if not sink:
+        return dw, db
+    wsink.mark()
+    if has_bias:
+        bsink.mark()
+    return None, None
+
+
 class _ConvFn(torch.autograd.Function):
     """y = act(scale * conv(pad(cat[x1,x2]), W) + b)  -- uegan_conv2d_fwd / dgrad / wgrad."""
 
     @staticmethod
-    def forward(ctx, x1, x2, weight, bias, cfg, sn, wkey, n_out=1, stats=None, ex=None):
+    def forward(ctx, x1, x2, weight, bias, cfg, sn, wkey, n_out=1, stats=None, ex=None, premasked=None):
         x1 = x1.contiguous()
         x2 = None if x2 is None else x2.contiguous()
         d = _desc(x1, x2, weight, cfg)
@@ -484,6 +507,9 @@ class _ConvFn(torch.autograd.Function):
                 stats.value = None
             _fwd_plain(d, x1, x2, ohwi, biasc, scale, y)
         ctx.cfg, ctx.sn, ctx.d, ctx.ihwo = cfg, sn, d, ihwo
+        # (premasked is the layer's static setting unless THIS call's consumer says otherwise: gam_hub takes over the activation backward of the
+        # encoder layers in front of the full-resolution attention modules only where the library offers the one-pass kernel)
+        ctx.premasked = cfg.premasked if premasked is None else bool(premasked)
         ctx.pack_version = cfg.packed.version
         ctx.has_x2, ctx.has_bias = x2 is not None, bias is not None
         ctx.wsink, ctx.bsink = _sink_of(weight), _sink_of(bias)
@@ -505,9 +531,9 @@ class _ConvFn(torch.autograd.Function):
         if len(gs) > 3:
             raise RuntimeError("conv: at most 3 consumers per activation")
         g = gs[0]
-        if len(gs) > 1 or (cfg.act != ACT_NONE and not cfg.premasked):
+        if len(gs) > 1 or (cfg.act != ACT_NONE and not ctx.premasked):
             dz = torch.empty_like(g)
-            act = ACT_NONE if cfg.premasked else cfg.act
+            act = ACT_NONE if ctx.premasked else cfg.act
             L.check(lib().uegan_act_bwd3(_dt(g), act, _p(g), _p(gs[1]) if len(gs) > 1 else None, _p(gs[2]) if len(gs) > 2 else None, _p(y),
                                          _p(dz), g.numel(), st))
         else:
@@ -534,29 +560,15 @@ class _ConvFn(torch.autograd.Function):
             wsb = lib().uegan_conv2d_wgrad_workspace_bytes(C.byref(d))
             ws = torch.empty((max(wsb, 4) + 3) // 4, dtype=torch.float32, device=g.device)
             wsink, bsink = ctx.wsink, ctx.bsink
-            # straight into the optimizer's flat bucket when both gradients live there (beta = 1 after the first touch); the
-            # spectral-norm correction below works in place on THIS call's gradient, so it needs the first touch
-            sink = (wsink is not None and ctx.needs_input_grad[2] and (not ctx.has_bias or (bsink is not None and bsink.dirty == wsink.dirty))
-                    and (sn is None or not wsink.dirty))
-            if sink:
-                dw, db, acc = wsink.view, (bsink.view if ctx.has_bias else None), (3 if wsink.dirty else 0)
-            else:
-                # (a column-slice conv writes only its own columns: the rest of the gradient is zero)
-                dw = (torch.zeros if cfg.cin_used is not None else torch.empty)(weight.shape, dtype=torch.float32, device=g.device)
-                db = torch.empty((d.Cout_w,), dtype=torch.float32, device=g.device) if ctx.has_bias else None
-                acc = 0
+            sink, dw, db, acc = _wgrad_target(wsink, bsink, ctx.has_bias, ctx.needs_input_grad[2], sn, weight, cfg, d.Cout_w, g.device)
             L.check(lib().uegan_conv2d_wgrad_acc(C.byref(d), _p(x1), _p(x2), _p(dz), _p(scale), _p(dw), _p(db), _p(ws), wsb, acc, st))
             if sn is not None:
                 wd = weight.detach()
                 rows, cols = wd.shape[0], wd[0].numel()
                 tmp = torch.empty((lib().uegan_specnorm_grad_workspace_floats(),), dtype=torch.float32, device=g.device)
                 L.check(lib().uegan_specnorm_grad(_p(dw), _p(wd), _p(sn.u), _p(sn.v), _p(sn.sigma), _p(dw), rows, cols, _p(tmp), st))
-            if sink:
-                wsink.mark()
-                if ctx.has_bias:
-                    bsink.mark()
-                dw = db = None
-        return dx1, dx2, dw, db, None, None, None, None, None, None
+            dw, db = _wgrad_done(sink, wsink, bsink, ctx.has_bias, dw, db)
+        return dx1, dx2, dw, db, None, None, None, None, None, None, None
 
 
 class StatsHolder:
@@ -568,10 +580,11 @@ class StatsHolder:
         self.value = None
 
 
-def conv2d(x1, x2, weight, bias, cfg, sn=None, wkey=None, n_out=1, stats=None, ex=None):
+def conv2d(x1, x2, weight, bias, cfg, sn=None, wkey=None, n_out=1, stats=None, ex=None, premasked=None):
     """n_out > 1: returns n_out aliases of the output, one per consumer (their gradients are summed inside the activation backward);
-    ex: a ConvExtras (hi + lo pairs, product / residual epilogue: uegan_conv2d_fwd_ex) -- its outputs are plain tensors outside the graph"""
-    return _ConvFn.apply(x1, x2, weight, bias, cfg, sn, wkey, n_out, stats, ex)
+    ex: a ConvExtras (hi + lo pairs, product / residual epilogue: uegan_conv2d_fwd_ex) -- its outputs are plain tensors outside the graph;
+    premasked: this call's value of ConvCfg.premasked (None: the layer's)"""
+    return _ConvFn.apply(x1, x2, weight, bias, cfg, sn, wkey, n_out, stats, ex, premasked)
 
 
 def specnorm_sigma(weight_orig, u, v, do_iter):
@@ -630,6 +643,18 @@ class _MaxPool2x2(torch.autograd.Function):
         return gx, None
 
 
+def _instnorm_into(x, y, pre):
+    """y = InstanceNorm(x) -> the [2, B, C] (mean, rstd) used: `pre` where the producing convolution delivered it (one pass), else computed here"""
+    B, H, W, Cc = x.shape
+    if pre is not None:
+        L.check(lib().uegan_instnorm_apply(_dt(x), _p(x), _p(y), _p(pre[0]), _p(pre[1]), B, H * W, Cc, _stream()))
+        return pre
+    stats = torch.empty((2, B, Cc), dtype=torch.float32, device=x.device)
+    tmp = torch.empty((lib().uegan_reduce_workspace_floats(B, H * W, Cc),), dtype=torch.float32, device=x.device)
+    L.check(lib().uegan_instnorm_fwd(_dt(x), _p(x), _p(y), _p(stats[0]), _p(stats[1]), _p(tmp), B, H * W, Cc, IN_EPS, _stream()))
+    return stats
+
+
 class _InstNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pre=None, x_lo=None, lo_out=None):
@@ -646,13 +671,8 @@ class _InstNorm(torch.autograd.Function):
             ylo = torch.empty_like(x)
             L.check(lib().uegan_instnorm_apply_pair(_dt(x), _p(x), _p(x_lo), _p(y), _p(ylo), _p(stats[0]), _p(stats[1]), B, H * W, Cc, _stream()))
             lo_out.append(ylo)
-        elif pre is not None:
-            stats = pre
-            L.check(lib().uegan_instnorm_apply(_dt(x), _p(x), _p(y), _p(stats[0]), _p(stats[1]), B, H * W, Cc, _stream()))
         else:
-            stats = torch.empty((2, B, Cc), dtype=torch.float32, device=x.device)
-            tmp = torch.empty((lib().uegan_reduce_workspace_floats(B, H * W, Cc),), dtype=torch.float32, device=x.device)
-            L.check(lib().uegan_instnorm_fwd(_dt(x), _p(x), _p(y), _p(stats[0]), _p(stats[1]), _p(tmp), B, H * W, Cc, IN_EPS, _stream()))
+            stats = _instnorm_into(x, y, pre)
         ctx.save_for_backward(y, stats)
         return y
 
@@ -665,6 +685,59 @@ class _InstNorm(torch.autograd.Function):
         tmp = torch.empty((lib().uegan_reduce_workspace_floats(B, H * W, Cc),), dtype=torch.float32, device=y.device)
         L.check(lib().uegan_instnorm_bwd(_dt(y), _p(g), _p(y), _p(stats[1]), _p(dx), _p(tmp), B, H * W, Cc, _stream()))
         return dx, None, None, None
+
+
+def gam_bwd_ws_bytes(dtype, B, HW, Cc, x_act):
+    """workspace of the one-pass attention backward (uegan_gam_bwd) for an encoder activation [B, HW, Cc] in `dtype` that act `x_act` produced; 0: the
+    library declines (fp32 storage, C other than 32 / 64, the UEGAN_TUNE_GAM_BWD knob off) and the caller keeps the separate passes"""
+    if dtype == torch.float32:
+        return 0
+    return lib().uegan_gam_bwd_ws_bytes(1, B, HW, Cc, x_act)
+
+
+class _GamHub(torch.autograd.Function):
+    """An encoder activation x and its attention module y = IN(W[:, :C] x) (models.GAM) as ONE node: forward -> (x once per remaining consumer ..., y);
+    backward receives all of their gradients in one call and issues uegan_gam_bwd, which returns the gradient of the encoder convolution's
+    PRE-activation (x's activation backward included: that convolution runs with premasked=True) and the module's weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, cfg, x_act, n_x, wsb):
+        x = x.contiguous()
+        holder = StatsHolder()
+        z, d, ihwo = raw_conv_fwd(x, None, weight, None, cfg, stats=holder)
+        y = torch.empty_like(z)
+        stats = _instnorm_into(z, y, holder.value)
+        ctx.cfg, ctx.d, ctx.ihwo, ctx.pack_version = cfg, d, ihwo, cfg.packed.version
+        ctx.x_act, ctx.wsb, ctx.wsink = x_act, wsb, _sink_of(weight)
+        ctx.save_for_backward(x, y, stats, weight)
+        return tuple(x.view_as(x) for _ in range(n_x)) + (y,)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        x, y, stats, weight = ctx.saved_tensors
+        cfg, d = ctx.cfg, ctx.d
+        gy = gs[-1]
+        adds = [g.contiguous() for g in gs[:-1] if g is not None]
+        if gy is None or len(adds) > 2:
+            raise RuntimeError("gam_hub backward: the attention output's gradient and at most two further gradients of x expected")
+        if cfg.packed.ihwo is ctx.ihwo and cfg.packed.version != ctx.pack_version:
+            raise RuntimeError("gam_hub backward: the module's weight was updated by an optimizer step after this forward; run backward() before step()")
+        gy = gy.contiguous()
+        _chk(gy, *adds)
+        B, H, W, Cc = x.shape
+        dz_enc = torch.empty_like(x)
+        ws = torch.empty(((ctx.wsb + 3) // 4,), dtype=torch.float32, device=x.device)
+        sink, dw, _, acc = _wgrad_target(ctx.wsink, None, False, ctx.needs_input_grad[1], None, weight, cfg, 0, x.device)
+        L.check(lib().uegan_gam_bwd(_dt(x), _p(gy), _p(y), _p(x), _p(stats[1]), _p(ctx.ihwo), _p(adds[0]) if adds else None,
+                                    _p(adds[1]) if len(adds) > 1 else None, ctx.x_act, _p(dz_enc), _p(dw), d.Cin_total, d.Cin_w, 1 if acc else 0,
+                                    _p(ws), ctx.wsb, B, H * W, Cc, _stream()))
+        dw, _ = _wgrad_done(sink, ctx.wsink, None, False, dw, None)
+        return dz_enc, dw, None, None, None, None
+
+
+def gam_hub(x, weight, cfg, x_act, n_x, wsb):
+    """-> (x, ... n_x aliases ..., IN(conv1x1(x))): see _GamHub; wsb: gam_bwd_ws_bytes(x, x_act), non-zero"""
+    return _GamHub.apply(x, weight, cfg, x_act, n_x, wsb)
 
 
 class _Mul(torch.autograd.Function):
