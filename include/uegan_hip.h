@@ -350,6 +350,11 @@ int uegan_quantize_u8(const float* x_nchw, uint8_t* y_nhwc, int B, int C, int H,
  * save_image(torch.cat([denorm(a), denorm(b), ...], 3)) writes for samples, validation and test montages (trainer.py:182-183,244-245,
  * tester.py:73-74), with uegan_quantize_u8's arithmetic.  srcs_nchw is a HOST array of n device pointers (passed to the kernel by value). */
 int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream);
+/* uegan_montage_u8 with a window: the sources are [B][C][Hs][Ws] planes and only their top-left H x W corner (H <= Hs, W <= Ws) is
+ * quantised and laid side by side, y[B][H][n*W][C].  Hs == H and Ws == W is uegan_montage_u8; n == 1 is the cropped save_image
+ * quantisation: what native-size inference writes after the generator ran on the image extended to multiples of 16. */
+int uegan_montage_crop_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
+                          uegan_stream_t stream);
 /* Per image b < B of two uint8 NHWC stacks, after cropping crop_border pixels on every side (CalcPSNR.py:24,56 / CalcSSIM.py:24,56):
  *   sqdiff_sum[b] (may be NULL) = sum (a - b)^2               -> PSNR = 10 log10(255^2 / (sqdiff_sum / n)), CalcPSNR.py:85-92
  *   ssim_sum[b]   (may be NULL) = sum over channels and valid 7x7 windows of the SSIM index with skimage's defaults as called at
@@ -370,6 +375,12 @@ int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, double*
  * the layout InputFetcher hands to the trainer (:124-127).  tmp: DEVICE uint8 [B][in_h][out_w][3] scratch.  Bit-exact. */
 int uegan_input_transform(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
                           const int32_t* vtab, int vk, const int32_t* flips, uint8_t* tmp, float* out_nchw, uegan_stream_t stream);
+/* Native-size input: ToTensor + Normalize(0.5, 0.5) of B decoded images, DEVICE uint8 [B][h][w][3], with NO resize, extended by
+ * reflection at the bottom and right to hp >= h rows and wp >= w columns (hp - h < h, wp - w < w, wp a multiple of 4, out_nchw 16-byte
+ * aligned) in one pass: out_nchw fp32 [B][3][hp][wp], row y >= h = source row 2(h-1) - y, column x >= w = source column 2(w-1) - x --
+ * bit for bit F.pad(uegan_input_transform at out size = in size, (0, wp-w, 0, hp-h), mode="reflect").  The valid window stays in the
+ * top-left corner; uegan_montage_crop_u8 cuts it back out of the generator's output. */
+int uegan_native_input(const uint8_t* pixels, int B, int h, int w, int hp, int wp, float* out_nchw, uegan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * NIMA aesthetic scorer (metrics/NIMA/CalcNIMA.py: MobileNetV2 trunk + ReLU -> Linear(1280, 10) -> Softmax), eval mode, fp32 only.

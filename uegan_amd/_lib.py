@@ -155,6 +155,8 @@ SIGNATURES = {
     "uegan_copy_images": (c_int, [c_vp, c_vp, c_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_int, c_i64, c_vp]),
     "uegan_quantize_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_montage_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "uegan_montage_crop_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "uegan_native_input": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_nima_prepare": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),

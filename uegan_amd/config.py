@@ -40,7 +40,7 @@ _MODEL = [
     ("adv_loss_type", str, "rahinge", "quality loss: ls|original|hinge|rahinge|rals"),
     ("image_size", int, 512, "side of the random training crop"),
     ("resize_size", int, 256, "side of the training image after resizing the crop"),
-    ("test_img_size", int, 512, "side of validation and test images after resizing"),
+    ("test_img_size", int, 512, "side of validation and test images after resizing; 0: no resizing, every image is enhanced and scored at its own size"),
     ("g_conv_dim", int, 32, "filters of the generator's first layer"),
     ("d_conv_dim", int, 32, "filters of the discriminator's first layer"),
     ("shuffle", str2bool, True, "shuffle the training set"),

@@ -99,9 +99,73 @@ __global__ void resample_v_unit_kernel(const uint8_t* tmp, float* out, const int
   }
 }
 
+// ---- native-size input: ToTensor + Normalize of the image as it is, extended by reflection at the bottom and right to [hp][wp] (multiples of 16
+// for the generator) in the same pass.  HBM-bound: 3 B read + 12 B written per output pixel.  One thread = 4 neighbouring output pixels of one row:
+// one 16-byte store per plane (wp % 4 == 0 and out 16-byte aligned: the launcher checks both).  DW: w % 4 == 0 and pixels 4-byte aligned, so a
+// group inside the image is 12 contiguous bytes at a multiple of 12 from an aligned base -> 3 whole dwords; groups in the extension (their source
+// columns run backwards) and every group of the other case read byte by byte. ----
+constexpr int NATIVE_THREADS = 256;
+constexpr int NATIVE_MAX_BLOCKS = 2048;       // grid cap: 8 blocks (32 waves) per CU on 256 CUs, the rest by grid stride
+constexpr int NATIVE_VEC = 4;                 // output pixels per thread (uegan_amd/data.py mirrors these three numbers)
+
+__device__ __forceinline__ float norm_u8(uint32_t v) { return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 0.5f); }
+
+template <bool DW>
+__global__ void native_input_kernel(const uint8_t* pix, float* out, size_t rows, int h, int w, int hp, int wp) {
+  const int wq = wp / NATIVE_VEC;
+  const size_t items = rows * wq;               // rows = B * hp
+  const size_t plane = (size_t)hp * wp;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
+    const int x0 = (int)(i % wq) * NATIVE_VEC;
+    const size_t row = i / wq;                  // b * hp + y
+    const size_t b = row / hp;
+    const int y = (int)(row - b * hp);
+    const int sy = y < h ? y : 2 * (h - 1) - y;
+    const uint8_t* src = pix + (b * h + sy) * (size_t)w * 3;
+    uint32_t v[NATIVE_VEC * 3];                  // v[3 * j + c]: pixel x0 + j, channel c
+    if (DW && x0 + NATIVE_VEC <= w) {
+      const uint32_t* p = reinterpret_cast<const uint32_t*>(src + (size_t)x0 * 3);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const uint32_t u = p[d];
+        v[4 * d] = u & 255u; v[4 * d + 1] = (u >> 8) & 255u; v[4 * d + 2] = (u >> 16) & 255u; v[4 * d + 3] = u >> 24;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NATIVE_VEC; ++j) {
+        const int x = x0 + j;
+        const uint8_t* p = src + (size_t)(x < w ? x : 2 * (w - 1) - x) * 3;
+        v[3 * j] = p[0]; v[3 * j + 1] = p[1]; v[3 * j + 2] = p[2];
+      }
+    }
+    float* o = out + (b * 3 * hp + y) * (size_t)wp + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<f32x4*>(o + c * plane) = f32x4{norm_u8(v[c]), norm_u8(v[3 + c]), norm_u8(v[6 + c]), norm_u8(v[9 + c])};
+  }
+}
+
 }  // namespace uegan
 
 using namespace uegan;
+
+extern "C" int uegan_native_input(const uint8_t* pixels, int B, int h, int w, int hp, int wp, float* out_nchw, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(pixels && out_nchw, "native_input: null pointer");
+  UEGAN_CHECK_ARG(B >= 1 && h >= 1 && w >= 1, "native_input: bad geometry (B %d, %d x %d)", B, h, w);
+  // a reflected index 2(n-1) - i stays inside [0, n) only while the extension is shorter than the image
+  UEGAN_CHECK_ARG(hp >= h && hp - h < h && wp >= w && wp - w < w, "native_input: %d x %d cannot be extended by reflection to %d x %d", h, w, hp, wp);
+  UEGAN_CHECK_ARG(wp % NATIVE_VEC == 0 && (uintptr_t)out_nchw % 16 == 0, "native_input: the padded width (%d) must be a multiple of %d and the output 16-byte aligned",
+                  wp, NATIVE_VEC);
+  const size_t rows = (size_t)B * hp;
+  const size_t items = rows * (wp / NATIVE_VEC);
+  const size_t want = (items + NATIVE_THREADS - 1) / NATIVE_THREADS;
+  const dim3 grid((unsigned)(want < (size_t)NATIVE_MAX_BLOCKS ? want : (size_t)NATIVE_MAX_BLOCKS)), block(NATIVE_THREADS);
+  const bool dw = w % 4 == 0 && (uintptr_t)pixels % 4 == 0;
+  if (dw) hipLaunchKernelGGL((native_input_kernel<true>), grid, block, 0, (hipStream_t)stream, pixels, out_nchw, rows, h, w, hp, wp);
+  else hipLaunchKernelGGL((native_input_kernel<false>), grid, block, 0, (hipStream_t)stream, pixels, out_nchw, rows, h, w, hp, wp);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
 
 extern "C" int uegan_nima_prepare(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
                                   const int32_t* vtab, int vk, uint8_t* tmp, float* out, int cpad, uegan_stream_t stream) {

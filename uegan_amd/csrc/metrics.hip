@@ -45,7 +45,8 @@ __global__ void quantize_u8_kernel(const float* x, uint8_t* y, int B, int C, int
 
 // ---- up to four [-1,1] NCHW fp32 images side by side -> ONE uint8 NHWC image [B][H][n*W][C], panel k in columns [k*W, (k+1)*W): what
 // save_image(torch.cat([denorm(a), denorm(b), ...], 3)) writes (trainer.py:182-183,244-245, tester.py:73-74), with quantize_u8_kernel's
-// arithmetic.  The source pointers travel by value, like CopyTable.  HBM-bound: 4 B read + 1 B written per element, each exactly once. ----
+// arithmetic.  The source pointers travel by value, like CopyTable.  HBM-bound: 4 B read + 1 B written per element, each exactly once.
+// The sources are [B][C][Hs][Ws] planes of which the top-left H x W window is taken (uegan_montage_crop_u8; uegan_montage_u8: Hs = H, Ws = W). ----
 constexpr int MONTAGE_MAX_SRCS = 4;
 constexpr int MONTAGE_THREADS = 256;
 constexpr int MONTAGE_MAX_BLOCKS = 1024;      // grid cap: 4 blocks (16 waves) per CU on 256 CUs, the rest by grid stride
@@ -62,10 +63,10 @@ __device__ __forceinline__ uint32_t quantize_u8(float x) {
   return (uint32_t)(uint8_t)v;                 // truncation, like Tensor.to(torch.uint8)
 }
 
-// vector path (W % 4 == 0, sources 16-byte and y 4-byte aligned): one thread = 4 neighbouring pixels of one panel row: one 16-byte load per
+// vector path (W % 4 == 0, Ws % 4 == 0, sources 16-byte and y 4-byte aligned): one thread = 4 neighbouring pixels of one panel row: one 16-byte load per
 // plane (a wave reads 1 KiB of a plane row in one instruction), C whole dwords stored (4 * C bytes: the 4 pixels' bytes are contiguous in NHWC)
 template <int C>
-__global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int H, int W) {
+__global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int Hs, int Ws, int H, int W) {
   const int wq = W / MONTAGE_VEC;
   const size_t items = rows * n * wq;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
@@ -74,11 +75,11 @@ __global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t r
     const int k = (int)(t % n);
     const size_t row = t / n;                  // b * H + h
     const size_t b = row / H, h = row - b * H;
-    const float* src = s.p[k] + ((b * C) * H + h) * W + (size_t)q * MONTAGE_VEC;
+    const float* src = s.p[k] + ((b * C) * Hs + h) * Ws + (size_t)q * MONTAGE_VEC;
     uint32_t by[MONTAGE_VEC * C];              // byte j of the 4 * C output bytes = pixel j / C, channel j % C
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * H * W);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)c * Hs * Ws);
       by[0 * C + c] = quantize_u8(v[0]);
       by[1 * C + c] = quantize_u8(v[1]);
       by[2 * C + c] = quantize_u8(v[2]);
@@ -91,7 +92,7 @@ __global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t r
 }
 
 // scalar path (any width, any alignment, any C): one thread = one output pixel
-__global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int C, int H, int W) {
+__global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int C, int Hs, int Ws, int H, int W) {
   const size_t items = rows * n * W;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
     const int w = (int)(i % W);
@@ -99,8 +100,8 @@ __global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows,
     const int k = (int)(t % n);
     const size_t row = t / n;
     const size_t b = row / H, h = row - b * H;
-    const float* src = s.p[k] + ((b * C) * H + h) * W + w;
-    for (int c = 0; c < C; ++c) y[i * C + c] = (uint8_t)quantize_u8(src[(size_t)c * H * W]);
+    const float* src = s.p[k] + ((b * C) * Hs + h) * Ws + w;
+    for (int c = 0; c < C; ++c) y[i * C + c] = (uint8_t)quantize_u8(src[(size_t)c * Hs * Ws]);
   }
 }
 
@@ -281,15 +282,17 @@ extern "C" int uegan_quantize_u8(const float* x_nchw, uint8_t* y_nhwc, int B, in
   return UEGAN_OK;
 }
 
-extern "C" int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream) {
-  UEGAN_CHECK_ARG(srcs_nchw && y_nhwc && B > 0 && C > 0 && H > 0 && W > 0, "bad montage_u8 args");
-  UEGAN_CHECK_ARG(n >= 1 && n <= MONTAGE_MAX_SRCS, "montage_u8 takes 1..%d images (got %d)", MONTAGE_MAX_SRCS, n);
+static int montage_launch(const char* who, const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
+                          uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(srcs_nchw && y_nhwc && B > 0 && C > 0 && H > 0 && W > 0, "bad %s args", who);
+  UEGAN_CHECK_ARG(H <= Hs && W <= Ws, "%s: the %d x %d window does not fit its %d x %d source", who, H, W, Hs, Ws);
+  UEGAN_CHECK_ARG(n >= 1 && n <= MONTAGE_MAX_SRCS, "%s takes 1..%d images (got %d)", who, MONTAGE_MAX_SRCS, n);
   MontageSrcs s;
-  bool vec = W % MONTAGE_VEC == 0 && (uintptr_t)y_nhwc % 4 == 0 && (C == 1 || C == 3 || C == 4);
+  bool vec = W % MONTAGE_VEC == 0 && Ws % MONTAGE_VEC == 0 && (uintptr_t)y_nhwc % 4 == 0 && (C == 1 || C == 3 || C == 4);
   for (int k = 0; k < MONTAGE_MAX_SRCS; ++k) {
     s.p[k] = k < n ? srcs_nchw[k] : nullptr;
     if (k < n) {
-      UEGAN_CHECK_ARG(srcs_nchw[k], "montage_u8: null image %d", k);
+      UEGAN_CHECK_ARG(srcs_nchw[k], "%s: null image %d", who, k);
       vec = vec && (uintptr_t)srcs_nchw[k] % 16 == 0;
     }
   }
@@ -298,12 +301,21 @@ extern "C" int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y
   const size_t want = (items + MONTAGE_THREADS - 1) / MONTAGE_THREADS;
   const dim3 grid((unsigned)(want < (size_t)MONTAGE_MAX_BLOCKS ? want : (size_t)MONTAGE_MAX_BLOCKS)), block(MONTAGE_THREADS);
   hipStream_t st = (hipStream_t)stream;
-  if (!vec) hipLaunchKernelGGL(montage_u8_kernel, grid, block, 0, st, s, n, y_nhwc, rows, C, H, W);
-  else if (C == 3) hipLaunchKernelGGL((montage_u8_vec_kernel<3>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
-  else if (C == 1) hipLaunchKernelGGL((montage_u8_vec_kernel<1>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
-  else hipLaunchKernelGGL((montage_u8_vec_kernel<4>), grid, block, 0, st, s, n, y_nhwc, rows, H, W);
+  if (!vec) hipLaunchKernelGGL(montage_u8_kernel, grid, block, 0, st, s, n, y_nhwc, rows, C, Hs, Ws, H, W);
+  else if (C == 3) hipLaunchKernelGGL((montage_u8_vec_kernel<3>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
+  else if (C == 1) hipLaunchKernelGGL((montage_u8_vec_kernel<1>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
+  else hipLaunchKernelGGL((montage_u8_vec_kernel<4>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
+}
+
+extern "C" int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream) {
+  return montage_launch("montage_u8", srcs_nchw, n, y_nhwc, B, C, H, W, H, W, stream);
+}
+
+extern "C" int uegan_montage_crop_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
+                                     uegan_stream_t stream) {
+  return montage_launch("montage_crop_u8", srcs_nchw, n, y_nhwc, B, C, Hs, Ws, H, W, stream);
 }
 
 extern "C" int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, double* sqdiff_sum, double* ssim_sum, int B, int H, int W,

@@ -108,6 +108,54 @@ def input_transform(pixels, out_size, flips=None, out=None, stream=None):
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# native size: no resize, the image extended by reflection to the multiples of 16 the generator needs
+# --------------------------------------------------------------------------------------------------------------------
+NATIVE_MULTIPLE = 16                  # Generator.forward: four stride-2 stages
+NATIVE_MIN_SIDE = 32
+# per-image cap of the padded area.  8 * 1024^2 is the per-launch element count the suite has run the generator at (8 x 3 x 1024^2): a statement
+# of what has been exercised, not a measured limit
+NATIVE_MAX_PIXELS = 8 * 1024 * 1024
+# the launcher's constants (csrc/input.hip: NATIVE_MAX_BLOCKS, NATIVE_THREADS, NATIVE_VEC): above MAX_BLOCKS * THREADS groups of VEC output
+# pixels the kernel loops by grid stride -- tests/test_native.py crosses the threshold on both read paths
+NATIVE_MAX_BLOCKS, NATIVE_THREADS, NATIVE_VEC = 2048, 256, 4
+
+
+def padded_size(h, w):
+    """(hp, wp): the next multiples of 16 of an h x w image, the size the generator runs at in native mode"""
+    m = NATIVE_MULTIPLE
+    return (int(h) + m - 1) // m * m, (int(w) + m - 1) // m * m
+
+
+def check_native_size(h, w):
+    """raise ValueError unless an h x w image can be enhanced at its own size: both sides >= 32, padded area <= NATIVE_MAX_PIXELS.  Returns (hp, wp)."""
+    if h < NATIVE_MIN_SIDE or w < NATIVE_MIN_SIDE:
+        raise ValueError("native-size inference needs both sides >= %d (got %d x %d)" % (NATIVE_MIN_SIDE, h, w))
+    hp, wp = padded_size(h, w)
+    if hp * wp > NATIVE_MAX_PIXELS:
+        raise ValueError("native-size inference: %d x %d pads to %d x %d = %d pixels, above the %d this package has been exercised at"
+                         % (h, w, hp, wp, hp * wp, NATIVE_MAX_PIXELS))
+    return hp, wp
+
+
+def native_input(pixels):
+    """pixels: uint8 [B, h, w, 3] on the device (decoded RGB images) -> fp32 [B, 3, hp, wp] in [-1, 1], (hp, wp) = padded_size(h, w):
+    ToTensor + Normalize(0.5, 0.5) and the reflection extension at the bottom and right in one pass (uegan_native_input) -- bit for bit
+    `F.pad(input_transform(pixels, (h, w)), (0, wp - w, 0, hp - h), mode="reflect")`; the image itself is out[:, :, :h, :w]."""
+    if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() != 4 or pixels.shape[3] != 3 or not pixels.is_contiguous():
+        raise ValueError("native_input expects a contiguous uint8 [B, h, w, 3] tensor")
+    B, h, w, _ = pixels.shape
+    hp, wp = check_native_size(h, w)
+    if B < 1:
+        raise ValueError("native_input: empty batch")
+    if not L.is_emulated() and not pixels.is_cuda:
+        raise RuntimeError("uegan_amd ops need CUDA/HIP tensors (there is no CPU path)")
+    out = torch.empty((B, 3, hp, wp), dtype=torch.float32, device=pixels.device)
+    stream = None if L.is_emulated() else torch.cuda.current_stream().cuda_stream
+    L.check(lib().uegan_native_input(_p(pixels), B, h, w, hp, wp, _p(out), stream))
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------------
 # datasets: file listing only
 # --------------------------------------------------------------------------------------------------------------------
 def listdir(dname):
@@ -175,6 +223,9 @@ def draw_train_params(h, w, crop, generator=None):
 
 
 Batch = collections.namedtuple("Batch", ["img_exp", "img_raw", "img_name"])
+# a batch of the native mode (get_test_loader(img_size=0)): img_exp / img_raw are LISTS of uint8 [1,h,w,3] device tensors, one per sample (the
+# decoded files, nothing resized; sizes may differ within a batch), paths the (label file, raw file) pair of each sample
+NativeBatch = collections.namedtuple("NativeBatch", ["img_exp", "img_raw", "img_name", "paths"])
 
 
 class _Slot:
@@ -192,7 +243,8 @@ class _Slot:
         self.out = None
         self.copied = None
 
-    def ensure(self, nbytes, device, pinned, shared):
+    def ensure(self, nbytes, device, pinned, shared, mirror=True):
+        """mirror=False: no device copy of the buffer (the native mode uploads every batch into a buffer of its own)"""
         if self.host is not None and self.host.numel() >= nbytes:
             return
         if shared:
@@ -204,7 +256,7 @@ class _Slot:
                 self.registered = int(torch.cuda.cudart().cudaHostRegister(self.host.data_ptr(), self.host.numel(), 0)) == 0
         else:
             self.host = torch.empty((nbytes,), dtype=torch.uint8, pin_memory=pinned)
-        self.dev = torch.empty((self.host.numel(),), dtype=torch.uint8, device=device)
+        self.dev = torch.empty((self.host.numel(),), dtype=torch.uint8, device=device) if mirror else None
 
     def release(self):
         if self.shm is not None:
@@ -278,7 +330,9 @@ class DeviceLoader:
     DataLoader + InputFetcher deliver (data_loader.py:113-133), produced `prefetch` batches ahead of the consumer.
 
     train=True : RandomCrop(img_size) -> Resize(resize_size) -> flips      (get_train_loader, :72-90)
-    train=False: Resize(img_size) of the whole image                        (get_test_loader, :93-110)"""
+    train=False: Resize(img_size) of the whole image                        (get_test_loader, :93-110)
+    train=False, img_size=0: the native mode -- nothing is resized and nothing transformed; it iterates NativeBatch, the decoded bytes of every
+                 file as a uint8 [1,h,w,3] device tensor (tester.enhance_native / run_test take them from there)"""
 
     def __init__(self, dataset, batch_size, img_size=512, resize_size=256, train=True, shuffle=True, drop_last=True, num_workers=8,
                  device=None, prefetch=2, generator=None, shard=None, shard_seed=0, workers="thread"):
@@ -291,6 +345,7 @@ class DeviceLoader:
         spawned pool, the launching script needs its `if __name__ == "__main__":` guard)."""
         self.dataset, self.batch_size, self.img_size, self.resize_size = dataset, batch_size, img_size, resize_size
         self.train, self.shuffle, self.drop_last = train, shuffle, drop_last
+        self.native = not train and img_size == 0
         self.generator = generator
         self.shard, self.shard_seed, self.epoch = shard, shard_seed, 0
         self.emulated = L.is_emulated()
@@ -373,9 +428,11 @@ class DeviceLoader:
                     plan.append((path, top, left, self.img_size, self.img_size, bits, off))
                     off += self.img_size * self.img_size * 3
                 else:
+                    if self.native:
+                        off = (off + 15) // 16 * 16      # every image starts 16-byte aligned: uegan_native_input reads whole dwords then
                     plan.append((path, 0, 0, h, w, 0, off))
                     off += h * w * 3
-        slot.ensure(off, self.device, pinned=not self.emulated, shared=self.shared)
+        slot.ensure(off, self.device, pinned=not self.emulated, shared=self.shared, mirror=not self.native)
         host = slot.host.numpy()
         slot.futures = []
         for path, top, left, h, w, bits, o in plan:
@@ -397,6 +454,10 @@ class DeviceLoader:
         S = self.resize_size if self.train else self.img_size
 
         def run(stream_handle):
+            if self.native:      # the batch IS the copied bytes: a buffer of its own (slot.dev is overwritten by the slot's next batch)
+                dev = torch.empty((slot.nbytes,), dtype=torch.uint8, device=self.device)
+                dev.copy_(slot.host[:slot.nbytes], non_blocking=True)
+                return dev
             slot.dev[:slot.nbytes].copy_(slot.host[:slot.nbytes], non_blocking=True)
             out = torch.empty((2 * B, 3, S, S), dtype=torch.float32, device=self.device)
             if self.train:
@@ -445,6 +506,13 @@ class DeviceLoader:
                 cur.wait_event(head.ready)
                 out.record_stream(cur)
             B = len(head.items)
+            if self.native:
+                imgs = [out[o:o + h * w * 3].view(1, h, w, 3) for _, _, _, h, w, _, o in head.plan]
+                paths = [(str(it[0]), str(it[1])) for it in head.items]
+                head.out = None
+                free.append(head)
+                yield NativeBatch(imgs[0::2], imgs[1::2], names, paths)
+                continue
             pair = out.view(B, 2, *out.shape[1:])
             head.out = None
             free.append(head)
@@ -459,7 +527,8 @@ def get_train_loader(root, img_size=512, resize_size=256, batch_size=8, shuffle=
 
 
 def get_test_loader(root, img_size=512, batch_size=8, shuffle=False, num_workers=4, device=None, generator=None, workers="thread"):
-    """data_loader.py:93-110"""
+    """data_loader.py:93-110.  img_size=0: the native mode of DeviceLoader (NativeBatch: the decoded files as they are, for tester.run_test /
+    tester.enhance_native to enhance at their own size)"""
     return DeviceLoader(ReferenceDataset(root), batch_size, img_size, img_size, False, shuffle, False, num_workers, device, generator=generator,
                         workers=workers)
 

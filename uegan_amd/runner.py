@@ -11,7 +11,9 @@ What differs from the reference, on purpose:
   * validation and test loaders are not shuffled (the reference shuffles both: main.py:37,45): the order only decides which file is written
     first, and a fixed order makes the logged means reproducible to the last bit.
   * the val loader resizes to --test_img_size (main.py:35-38 passes no size, so the reference validates at 512 whatever the flag says).
-  * PSNR / SSIM compare against the loader's label image, NIMA / PSNR / SSIM means are true means (tester.run_test's docstring).
+  * PSNR / SSIM compare against the loader's label image (--test_img_size 0: against the label file as it is), NIMA / PSNR / SSIM means are true
+    means (tester.run_test's docstring).
+  * --test_img_size 0 is the native size (tester.enhance_native): no resize, outputs at the size of their source, "sizes" in test_metrics.json.
   * the training loader draws from its own generator seeded with --seed (`loader_generator`), not from the global one: what validation or a
     sample draws never shifts the training data.
   * a step that prints nothing reads nothing from the device: the five losses are fetched (Trainer.loss_items) every --info_step only.

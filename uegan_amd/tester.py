@@ -3,8 +3,9 @@
     enhance(G, x)                     tester.py:58-67: `G.eval()`, `torch.no_grad()`, one `G(x)` per image
     GraphedGenerator(G, shape)        the same forward captured once into a hipGraph and replayed (batch-1 inference is
                                       ~60 dependent launches: launch latency, not arithmetic, sets its time)
+    enhance_native(G, pixels_u8)      an image at its OWN size: crop(G(reflect_extend(normalise(pixels)))), uint8 in, uint8 out
     montage_u8(a, b, ...)             `to_uint8_image(torch.cat([a, b, ...], 3))` in one launch: the side-by-side sample / compare images
-                                      (trainer.py:182-183,244-245, tester.py:73-74)
+                                      (trainer.py:182-183,244-245, tester.py:73-74); window=(H, W): of the images' top-left H x W corner
     to_uint8_image(x)                 what tester.py:70-71 writes to a PNG: denorm (utils.py:128-130) + torchvision save_image's
                                       mul(255).add(0.5).clamp(0,255).to(uint8), NHWC
     calculate_psnr / calculate_ssim   metrics/CalcPSNR.py:85-92 and metrics/CalcSSIM.py:63 (skimage defaults) with the 4-pixel
@@ -19,7 +20,7 @@ import math
 import torch
 
 from . import _lib as L
-from . import ops
+from . import data, ops
 
 CROP_BORDER = 4          # CalcPSNR.py:24 / CalcSSIM.py:24
 
@@ -71,8 +72,11 @@ class GraphedGenerator:
         return self.y
 
 
-def to_uint8_image(x):
-    """[-1,1] NCHW fp32 -> uint8 NHWC as tester.py:70-71 + torchvision.utils.save_image produce it (uegan_quantize_u8)."""
+def to_uint8_image(x, window=None):
+    """[-1,1] NCHW fp32 -> uint8 NHWC as tester.py:70-71 + torchvision.utils.save_image produce it (uegan_quantize_u8).
+    window=(H, W): of x[:, :, :H, :W] only, without the copy (uegan_montage_crop_u8 with one image)."""
+    if window is not None:
+        return montage_u8(x, window=window)
     x = x.detach().contiguous()
     if x.dtype != torch.float32 or x.dim() != 4:
         raise TypeError("to_uint8_image expects a float32 [B,C,H,W] tensor")
@@ -89,10 +93,12 @@ MONTAGE_MAX_BLOCKS, MONTAGE_THREADS, MONTAGE_VEC = 1024, 256, 4
 MONTAGE_MAX_IMAGES = 4
 
 
-def montage_u8(*images):
+def montage_u8(*images, window=None):
     """1..4 float32 [B,C,H,W] images of equal shape -> uint8 [B,H,n*W,C], image k in columns [k*W, (k+1)*W): bit for bit
     `to_uint8_image(torch.cat(images, 3))`, i.e. what `save_image(torch.cat([denorm(a), denorm(b), ...], 3))` writes for the sample and
-    compare montages (trainer.py:182-183,244-245, tester.py:73-74), in one launch that reads every source once (uegan_montage_u8)."""
+    compare montages (trainer.py:182-183,244-245, tester.py:73-74), in one launch that reads every source once (uegan_montage_u8).
+    window=(H, W): the same of every image's top-left corner, `to_uint8_image(torch.cat([x[:, :, :H, :W] for x in images], 3))`, read in
+    place (uegan_montage_crop_u8); a window that does not fit the images raises ValueError."""
     n = len(images)
     if not 1 <= n <= MONTAGE_MAX_IMAGES:
         raise ValueError("montage_u8 takes 1..%d images (got %d)" % (MONTAGE_MAX_IMAGES, n))
@@ -103,10 +109,40 @@ def montage_u8(*images):
             raise ValueError("montage_u8: the images must have one shape and one device (got %s and %s)" % (tuple(images[0].shape), tuple(x.shape)))
     xs = [x.detach().contiguous() for x in images]
     B, C, H, W = xs[0].shape
+    if window is not None:
+        Hs, Ws = H, W
+        H, W = (int(v) for v in window)
+        if not (1 <= H <= Hs and 1 <= W <= Ws):
+            raise ValueError("montage_u8: the %d x %d window does not fit the %d x %d images" % (H, W, Hs, Ws))
     y = torch.empty((B, H, n * W, C), dtype=torch.uint8, device=xs[0].device)
     ops._chk(y, *xs)
-    L.check(ops.lib().uegan_montage_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, H, W, ops._stream()))
+    if window is not None:
+        L.check(ops.lib().uegan_montage_crop_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, Hs, Ws, H, W, ops._stream()))
+    else:
+        L.check(ops.lib().uegan_montage_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, H, W, ops._stream()))
     return y
+
+
+def enhance_native(G, pixels_u8, compare=False):
+    """An image at its own size: uint8 [B,h,w,3] on the device (decoded RGB, both sides >= 32) -> the enhanced uint8 [B,h,w,3]; compare=True:
+    also the raw | enhanced montage uint8 [B,h,2w,3] (tester.py:73-74).  The mode is DEFINED as
+
+        crop(G(reflect_extend(normalise(pixels))))
+
+    normalise = ToTensor + Normalize(0.5, 0.5); reflect_extend = reflection at the bottom and right up to the next multiples of 16 (the
+    generator's four stride-2 stages), both in one pass (data.native_input); crop = the top-left h x w window, cut during the 8-bit
+    quantisation (uegan_montage_crop_u8).  Bit for bit `to_uint8_image(enhance(G, F.pad(data.input_transform(pixels, (h, w)), (0, wp - w, 0,
+    hp - h), mode="reflect")))[:, :h, :w]` in every storage mode.  One consequence: the attention modules' global moments are taken over the
+    extended image, so they include its up-to-15 reflected rows and columns (masked moments are not implemented).  The forward is eager
+    (there is no hipGraph per padded shape).  ValueError before any launch: a side below 32, a padded area above data.NATIVE_MAX_PIXELS
+    per image, anything but a contiguous uint8 [B,h,w,3] tensor."""
+    x = data.native_input(pixels_u8)
+    h, w = pixels_u8.shape[1:3]
+    fake = enhance(G, x)
+    q = to_uint8_image(fake, window=(h, w))
+    if not compare:
+        return q
+    return q, montage_u8(x, fake, window=(h, w))
 
 
 def _as_stack(img):
@@ -160,6 +196,11 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suff
     each enhanced image against `img_exp`, here straight from the device tensors.  Returns {"names", "psnr", "ssim", "mean_psnr",
     "mean_ssim"} (true means).
 
+    Native mode (a `data.get_test_loader(root, 0)` loader, whose batches hold the decoded files as uint8 lists): every sample goes through
+    `enhance_native` at its own size, the PNGs have the size of their source, the result gains "sizes" ([h, w] per image), and PSNR / SSIM
+    compare against the label FILE's own pixels -- what calc_psnr / calc_ssim read; a label of another size than its raw image raises
+    ValueError naming both files (CalcPSNR.py:87 raises on it too).  The restriction below is that of the resizing mode only.
+
     Restriction: the label here is the loader's `img_exp` -- the label FILE resized to the test size by the loader's transform
     (data_loader.py:95-99) and re-quantised to 8 bits -- whereas calc_psnr / calc_ssim read the ORIGINAL files of test_label_dir.  The
     numbers agree with the reference's when the label files already have the test size (the reference itself needs equal shapes:
@@ -171,41 +212,67 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suff
     nima: a `uegan_amd.nima.NIMA` module -> also "nima" / "nima_std" (per image) and "mean_nima" (true mean): what calc_nima (tester.py:91-94,
     on by default in the reference: config.py:80) computes from the saved files, here from the same 8-bit images on the device.  It needs no
     label: with metrics=False the loader's `img_exp` is never touched (the unpaired setting)."""
-    import os
-    names, psnr, ssim, nima_mean, nima_std = [], [], [], [], []
-    if nima is not None:
-        from . import nima as nima_mod
-    for d in (save_dir, compare_dir):
-        if d is not None:
-            os.makedirs(d, exist_ok=True)
+    rec = _TestRecord(metrics, nima, save_dir, compare_dir, tag, suffix, compare_suffix)
     for batch in loader:
+        if isinstance(batch.img_raw, (list, tuple)):      # native mode: the samples one by one, since their sizes may differ
+            if metrics:                                   # (before any launch)
+                for i, (raw, lab) in enumerate(zip(batch.img_raw, batch.img_exp)):
+                    if lab.shape != raw.shape:
+                        raise ValueError("Input images must have the same dimensions: label %s, raw %s are %d x %d and %d x %d"
+                                         % (batch.paths[i] + (lab.shape[1], lab.shape[2], raw.shape[1], raw.shape[2])))
+            for i, name in enumerate(batch.img_name):
+                raw = batch.img_raw[i]
+                res = enhance_native(G, raw, compare=compare_dir is not None)
+                q, pair = res if compare_dir is not None else (res, None)
+                rec.add([name], q, pair, batch.img_exp[i] if metrics else None)
+                rec.sizes.append([int(raw.shape[1]), int(raw.shape[2])])
+            continue
         fake = enhance(G, batch.img_raw)
         q = to_uint8_image(fake)
         pair = montage_u8(batch.img_raw, fake) if compare_dir is not None else None
-        if metrics:
-            ref = to_uint8_image(batch.img_exp)
-            psnr += calculate_psnr(q, ref)
-            ssim += calculate_ssim(q, ref)
-        if nima is not None:
-            m, d = nima_mod.score(nima, q)
-            nima_mean += m
-            nima_std += d
-        names += list(batch.img_name)
-        if save_dir is not None:
-            from PIL import Image
-            host = q.cpu().numpy()
-            for i, name in enumerate(batch.img_name):
-                Image.fromarray(host[i], "RGB").save(os.path.join(save_dir, "%s_%s_%s.png" % (name, tag, suffix)))
-        if pair is not None:
-            from PIL import Image
-            host = pair.cpu().numpy()
-            for i, name in enumerate(batch.img_name):
-                Image.fromarray(host[i], "RGB").save(os.path.join(compare_dir, "%s_%s_%s.png" % (name, tag, compare_suffix)))
-    out = {"names": names, "psnr": psnr, "ssim": ssim}
-    if metrics and names:
-        out["mean_psnr"], out["mean_ssim"] = mean_metric(psnr), mean_metric(ssim)
-    if nima is not None:
-        out["nima"], out["nima_std"] = nima_mean, nima_std
-        if names:
-            out["mean_nima"] = mean_metric(nima_mean)
-    return out
+        rec.add(list(batch.img_name), q, pair, to_uint8_image(batch.img_exp) if metrics else None)
+    return rec.result()
+
+
+class _TestRecord:
+    """what run_test does with the 8-bit images of one batch, whichever mode produced them: PSNR / SSIM against the 8-bit labels, NIMA, the PNGs"""
+
+    def __init__(self, metrics, nima, save_dir, compare_dir, tag, suffix, compare_suffix):
+        import os
+        self.metrics, self.nima, self.tag = metrics, nima, tag
+        self.dirs = ((save_dir, suffix), (compare_dir, compare_suffix))
+        self.names, self.psnr, self.ssim, self.nima_mean, self.nima_std, self.sizes = [], [], [], [], [], []
+        for d, _ in self.dirs:
+            if d is not None:
+                os.makedirs(d, exist_ok=True)
+
+    def add(self, names, q, pair, ref):
+        """q: enhanced uint8 [B,H,W,3]; pair: the raw | enhanced montage or None; ref: the labels as uint8 [B,H,W,3] or None"""
+        import os
+        if ref is not None:
+            self.psnr += calculate_psnr(q, ref)
+            self.ssim += calculate_ssim(q, ref)
+        if self.nima is not None:
+            from . import nima as nima_mod
+            m, d = nima_mod.score(self.nima, q)
+            self.nima_mean += m
+            self.nima_std += d
+        self.names += names
+        for (d, suffix), images in zip(self.dirs, (q, pair)):
+            if d is not None and images is not None:
+                from PIL import Image
+                host = images.cpu().numpy()
+                for i, name in enumerate(names):
+                    Image.fromarray(host[i], "RGB").save(os.path.join(d, "%s_%s_%s.png" % (name, self.tag, suffix)))
+
+    def result(self):
+        out = {"names": self.names, "psnr": self.psnr, "ssim": self.ssim}
+        if self.sizes:
+            out["sizes"] = self.sizes
+        if self.metrics and self.names:
+            out["mean_psnr"], out["mean_ssim"] = mean_metric(self.psnr), mean_metric(self.ssim)
+        if self.nima is not None:
+            out["nima"], out["nima_std"] = self.nima_mean, self.nima_std
+            if self.names:
+                out["mean_nima"] = mean_metric(self.nima_mean)
+        return out
