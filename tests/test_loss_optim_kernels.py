@@ -1,8 +1,8 @@
 """Kernel-level parity of everything between the discriminator's maps and the optimizer step, in every launch regime:
 
-* the relativistic losses (`ops.rahinge`, `variants.rals`) and the one-list terms (`variants.pred_loss`)          -- norm_loss.hip
-* the head-map form of the relativistic hinge (`uegan_rahinge_heads_fwd / _bwd`, fp32 / bf16 / fp16 storage)     -- norm_loss.hip
-* the multiscale reconstruction loss (`ops.multiscale_rec`)                                                      -- norm_loss.hip
+* the relativistic losses (`ops.rahinge`, `variants.rals`) and the one-list terms (`variants.pred_loss`)          -- loss.hip
+* the head-map form of the relativistic hinge (`uegan_rahinge_heads_fwd / _bwd`, fp32 / bf16 / fp16 storage)     -- loss.hip
+* the multiscale reconstruction loss (`ops.multiscale_rec`)                                                      -- loss.hip
 * the spectral-norm power iteration and gradient (`uegan_specnorm_*`)                                            -- optim_sn.hip
 * `uegan_sn_act_bwd` -> `uegan_sn_grad_finish` (unpadded form; the padded form keeps its test in test_ops.py)    -- act_bwd.hip
 * the multi-tensor Adam / RMSprop steps (`ops.FusedAdamL2`, `variants.FusedRMSprop`)                             -- optim_sn.hip
@@ -62,7 +62,7 @@ def held_scalar(family, backend, what, got, ref, tol):
 # --------------------------------------------------------------------------------------------------------------------
 # relativistic losses: rahinge / rals (losses.py:348-376, summed over the scales :393-409)
 # --------------------------------------------------------------------------------------------------------------------
-# norm_loss.hip: RB = 64 block partials per scale and quantity, 256 threads x 4 = 1024 elements per block (ra_fill: nbx = min(RB,
+# loss.hip: RB = 64 block partials per scale and quantity, 256 threads x 4 = 1024 elements per block (ra_fill: nbx = min(RB,
 # ceil(max n / 1024))); the gradient kernel caps at 256 blocks.  8 192 -> 8 partials, 65 536 -> 64, 65 537 -> 64 and a second trip of
 # the grid-stride loop, 300 000 -> several trips of the reduction and of the gradient kernel.
 RA_SIZES = [1, 700, 8192, 65536, 65537, 300000]

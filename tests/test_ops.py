@@ -1295,3 +1295,37 @@ def test_conv_stream_kernel_scale_per_image_group(backend):
         _lib.check(lib.uegan_conv2d_dgrad_ws(C.byref(dd), dz.data_ptr(), ihwo2.data_ptr(), scale.data_ptr(), g1.data_ptr(), None, ws.data_ptr(), wsb, ops._stream()))
         refg = g0.float().cpu() * sc
         assert float((g1.float().cpu() - refg).abs().max()) <= 2.0 ** -7 * float(refg.abs().max()), stride
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_unknown_dtype_is_refused_before_any_launch(backend):
+    """A dtype that is neither UEGAN_F32 nor UEGAN_BF16 is an argument error of every storage-typed entry point (csrc/launch.h): one from each
+    of act_bwd.hip, norm.hip, elementwise.hip and loss.hip returns UEGAN_E_INVALID with a "bad dtype" message and leaves its outputs alone."""
+    import ctypes as C
+    dev = use_backend(backend)
+    lib = _lib.load()
+    E_INVALID, BAD, SENT = -1, 7, -777.0          # UEGAN_E_INVALID (include/uegan_hip.h)
+    st = ops._stream()
+    src = lambda *shape: torch.ones(*shape, device=dev)
+    out = lambda *shape: torch.full(shape, SENT, device=dev)
+    # fp32 buffers: large enough whichever storage type a kernel would take them for
+    g, a, dz = src(32), src(32), out(32)
+    x, y, mean, rstd = src(1, 4, 4, 8), out(1, 4, 4, 8), src(8), src(8)
+    p, q, prod = src(32), src(32), out(32)
+    ng, nb, cp, h, w = 2, 1, 8, 3, 3
+    maps = src(ng * nb, h, w, cp)
+    tab = (C.c_void_p * 1)(maps.data_ptr())
+    pix = (C.c_int64 * 1)(h * w)
+    pairs = (C.c_int32 * 2)(0, 1)
+    loss, tmp = out(1), out(lib.uegan_rahinge_heads_workspace_floats(1))
+    calls = [
+        ("uegan_act_bwd3", (BAD, ops.ACT_LRELU, g.data_ptr(), None, None, a.data_ptr(), dz.data_ptr(), 32, st), [dz]),
+        ("uegan_instnorm_apply", (BAD, x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), 1, 16, 8, st), [y]),
+        ("uegan_mul_fwd", (BAD, p.data_ptr(), q.data_ptr(), prod.data_ptr(), 32, st), [prod]),
+        ("uegan_rahinge_heads_fwd", (BAD, 1, tab, pix, nb, cp, ng, 1, pairs, 1, loss.data_ptr(), tmp.data_ptr(), st), [loss, tmp]),
+    ]
+    for name, args, outs in calls:
+        assert getattr(lib, name)(*args) == E_INVALID, name
+        assert b"bad dtype" in lib.uegan_last_error(), (name, lib.uegan_last_error())
+        for o in outs:
+            assert bool((o.cpu() == SENT).all()), name

@@ -1,6 +1,7 @@
 // Activation backward passes: plain, with gradients on the padded grid of a reflection-padded consumer, and the spectral-normalised trunk's
 // (the batched discriminator pass) with its projection partials.
 #include "conv_core.h"
+#include "launch.h"
 
 namespace uegan {
 
@@ -275,18 +276,8 @@ extern "C" int uegan_act_bwd3(int dtype, int act, const void* g, const void* g2,
                               uegan_stream_t stream) {
   UEGAN_CHECK_ARG(g && a && dz && n >= 0, "bad act_bwd args");
   if (n == 0) return UEGAN_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int epc = dtype == UEGAN_F32 ? 4 : 8;
-  const bool vec = n % epc == 0;
-  const size_t work = vec ? (size_t)n / epc : (size_t)n;
-  const int blocks = (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
-  if (dtype == UEGAN_F32) {
-    if (vec) hipLaunchKernelGGL((act_bwd_kernel<float, 4>), dim3(blocks), dim3(256), 0, s, (const float*)g, (const float*)g2, (const float*)g3, (const float*)a, (float*)dz, (size_t)n, act);
-    else hipLaunchKernelGGL((act_bwd_kernel<float, 1>), dim3(blocks), dim3(256), 0, s, (const float*)g, (const float*)g2, (const float*)g3, (const float*)a, (float*)dz, (size_t)n, act);
-  } else {
-    if (vec) hipLaunchKernelGGL((act_bwd_kernel<bf16_t, 8>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)g2, (const bf16_t*)g3, (const bf16_t*)a, (bf16_t*)dz, (size_t)n, act);
-    else hipLaunchKernelGGL((act_bwd_kernel<bf16_t, 1>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)g2, (const bf16_t*)g3, (const bf16_t*)a, (bf16_t*)dz, (size_t)n, act);
-  }
+  UEGAN_DISPATCH_TV(dtype, n % epc_of(dtype) == 0, hipLaunchKernelGGL((act_bwd_kernel<T, V>), dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream,
+                                                                      (const T*)g, (const T*)g2, (const T*)g3, (const T*)a, (T*)dz, (size_t)n, act));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -311,40 +302,30 @@ extern "C" int uegan_sn_act_bwd_p(int dtype, int act, const void* g, int pad_g, 
     UEGAN_CHECK_ARG(H > 0 && W > 0 && pix_per_group % ((int64_t)H * W) == 0 && pad_g < H && pad_g < W && pad_g2 < H && pad_g2 < W,
                     "sn_act_bwd: a padded-grid gradient needs the map size (H, W) and whole images per group");
   UEGAN_CHECK_ARG(!(pad_g || pad_g2) || pix_per_group < (1ll << 31), "sn_act_bwd: more than 2^31 pixels per group");
-  const int epc = dtype == UEGAN_F32 ? 4 : 8;
+  const int epc = epc_of(dtype);
   UEGAN_CHECK_ARG(C % epc == 0 && 256 % (C / epc) == 0, "sn_act_bwd: channel chunks per pixel must divide 256 (C = %d)", C);
   const int pl = 256 / (C / epc);
-  long long bx = (pix_per_group + pl * 4 - 1) / (pl * 4);
-  if (bx > SNB / 2) bx = SNB / 2;
-  if (bx < 1) bx = 1;
+  int bx = blocks_for((size_t)pix_per_group, pl * 4, SNB / 2);
   // padded-grid gradients: the pixels on the mirror ring go to blocks of their own (see the kernel); both kinds share the SNB partial slots
   SnRing ring = {0, 0, 0, 0};
-  int bx_main = (int)bx;
+  int bx_main = bx;
   if (pad_g || pad_g2) {
     ring.pmax = pad_g > pad_g2 ? pad_g : pad_g2;
     ring.ring_all = (H < 2 * ring.pmax + 3 || W < 2 * ring.pmax + 3) ? 1 : 0;
     ring.n_row = 2 * ring.pmax * W;
     ring.n_ring = ring.ring_all ? H * W : ring.n_row + 2 * ring.pmax * (H - 2 * ring.pmax);
     const long long ring_pix = (pix_per_group / ((long long)H * W)) * ring.n_ring;
-    long long brg = (ring_pix + pl - 1) / pl;
-    if (brg > SNB / 2) brg = SNB / 2;
-    if (brg < 1) brg = 1;
     if (ring.ring_all) bx_main = 0;
-    bx = bx_main + brg;
+    bx = bx_main + blocks_for((size_t)ring_pix, pl, SNB / 2);
   }
   // (the partial arrays are laid out for SNB blocks per group whatever the launch uses: the finish kernel is told the actual count)
   float* cpart = workspace;
   float* dbpart = workspace + (size_t)ngroups * SNB;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == UEGAN_F32)
-    hipLaunchKernelGGL((sn_act_bwd_kernel<float>), dim3((unsigned)bx, ngroups), dim3(256), 0, s, (const float*)g, (const float*)g2, (const float*)y, bias, nbias,
-                       inv_sigma, (float*)dz, cpart, dbpart, (long long)pix_per_group, C, act, pad_g, pad_g2, H, W, bx_main, ring);
-  else if (dtype == UEGAN_BF16)
-    hipLaunchKernelGGL((sn_act_bwd_kernel<bf16_t>), dim3((unsigned)bx, ngroups), dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)g2, (const bf16_t*)y, bias,
-                       nbias, inv_sigma, (bf16_t*)dz, cpart, dbpart, (long long)pix_per_group, C, act, pad_g, pad_g2, H, W, bx_main, ring);
-  else UEGAN_CHECK_ARG(false, "bad dtype %d", dtype);
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((sn_act_bwd_kernel<T>), dim3(bx, ngroups), dim3(256), 0, s, (const T*)g, (const T*)g2, (const T*)y, bias, nbias,
+                                              inv_sigma, (T*)dz, cpart, dbpart, (long long)pix_per_group, C, act, pad_g, pad_g2, H, W, bx_main, ring));
   UEGAN_CHECK_LAUNCH();
-  return (int)bx;                                    // > 0: the number of partial blocks per group (for uegan_sn_grad_finish)
+  return bx;                                         // > 0: the number of partial blocks per group (for uegan_sn_grad_finish)
 }
 
 // dz = (g + g2) * act'(a) with g / g2 optionally on padded grids (as above); a, dz: [B][H][W][C]
@@ -352,17 +333,12 @@ extern "C" int uegan_act_bwd_p(int dtype, int act, const void* g, int pad_g, con
                                int C, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(g && a && dz && B > 0 && H > 0 && W > 0 && C > 0, "bad act_bwd_p args");
   UEGAN_CHECK_ARG(pad_g >= 0 && pad_g2 >= 0 && (g2 || pad_g2 == 0) && pad_g < H && pad_g < W && pad_g2 < H && pad_g2 < W, "act_bwd_p: bad padding");
-  const int epc = dtype == UEGAN_F32 ? 4 : 8;
+  const int epc = epc_of(dtype);
   UEGAN_CHECK_ARG(C % epc == 0, "act_bwd_p: whole 16-byte chunks per pixel (C = %d)", C);
   const size_t work = (size_t)B * H * W * (C / epc);
   UEGAN_CHECK_ARG(work < (1ull << 32) - 8192ull * 256, "act_bwd_p: more than 2^32 chunks");
-  const int blocks = (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == UEGAN_F32)
-    hipLaunchKernelGGL((act_bwd_p_kernel<float>), dim3(blocks), dim3(256), 0, s, (const float*)g, pad_g, (const float*)g2, pad_g2, (const float*)a, (float*)dz, B, H, W, C, act);
-  else if (dtype == UEGAN_BF16)
-    hipLaunchKernelGGL((act_bwd_p_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)g, pad_g, (const bf16_t*)g2, pad_g2, (const bf16_t*)a, (bf16_t*)dz, B, H, W, C, act);
-  else UEGAN_CHECK_ARG(false, "bad dtype %d", dtype);
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((act_bwd_p_kernel<T>), dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, (const T*)g, pad_g, (const T*)g2, pad_g2,
+                                              (const T*)a, (T*)dz, B, H, W, C, act));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -372,8 +348,7 @@ extern "C" int uegan_sn_grad_finish(float* dw, float* db, const float* workspace
   UEGAN_CHECK_ARG(dw && workspace && u_hist && v_hist && nbx >= 1 && nbx <= SNB && ngroups >= 1 && ngroups <= 8 && rows > 0 && cols > 0 && rows <= C,
                   "bad sn_grad_finish args");
   const size_t n = (size_t)rows * cols;
-  int blocks = (int)((n + 1023) / 1024);
-  if (blocks > 512) blocks = 512;
+  int blocks = blocks_for(n, 1024, 512);
   const int nbb = (rows + 15) / 16;                  // blocks that also finish 16 bias channels each
   if (blocks < nbb) blocks = nbb;
   hipLaunchKernelGGL(sn_grad_finish_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dw, db, workspace, workspace + (size_t)ngroups * SNB, nbx,

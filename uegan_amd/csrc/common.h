@@ -202,7 +202,7 @@ __device__ __forceinline__ float act_grad_of_pre(float v, int act) {
   }
 }
 
-// Gradient of one fidelity-loss tap, weight * MSE(IN(x), IN(y)), w.r.t. x (norm_loss.hip percep_grad_kernel).  conv_tall_kernel's tap epilogue
+// Gradient of one fidelity-loss tap, weight * MSE(IN(x), IN(y)), w.r.t. x (norm.hip percep_grad_kernel).  conv_tall_kernel's tap epilogue
 // (conv_wide.hip) adds the same term to a data gradient and must agree with the stand-alone pass to the bit, so both evaluate it here: one
 // formula, one FMA contraction.  g = dL/dxh = k*(xh-yh), k = 2*weight*gscale/nel;  dx = rx*(g - mean(g) - xh*mean(g*xh)).
 __device__ __forceinline__ void percep_scalars(float weight, const float* gscale, int B, int HW, int C, float& k, float& inv_n) {

@@ -3,6 +3,7 @@
 // models.py:191-201 (bilinear x2 align_corners=True), torchvision VGG MaxPool2d(2,2), trainer.py:108 + losses.py:26-27
 // (input rescale + ImageNet normalisation, folded into the NCHW->NHWC conversion).
 #include "common.h"
+#include "launch.h"
 
 namespace uegan {
 
@@ -369,32 +370,9 @@ __global__ void maxpool2x2_bwd_kernel(const T* x, const T* gy, T* gx, int B, int
   }
 }
 
-// threads of a block that owns one row of n work items: whole waves, at most 256
-static inline int row_threads(size_t n) { return n >= 256 ? 256 : (int)((n + 63) / 64) * 64; }
-static inline int grid_for(size_t n, int cap = 8192) {
-  size_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  return (int)(b < (size_t)cap ? b : (size_t)cap);
-}
-
 }  // namespace uegan
 
 using namespace uegan;
-
-#define DISPATCH_T(dtype, ...)                                   \
-  do {                                                           \
-    if ((dtype) == UEGAN_F32) { using T = float; __VA_ARGS__; }  \
-    else if ((dtype) == UEGAN_BF16) { using T = bf16_t; __VA_ARGS__; } \
-    else { set_error("bad dtype %d", (int)(dtype)); return UEGAN_E_INVALID; } \
-  } while (0)
-// binds T and V (V = one 16-byte chunk per thread when `vec_ok`, else 1)
-#define DISPATCH_TV(dtype, vec_ok, ...)                                                               \
-  do {                                                                                                \
-    if ((dtype) == UEGAN_F32) { using T = float; if (vec_ok) { constexpr int V = 4; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } } \
-    else if ((dtype) == UEGAN_BF16) { using T = bf16_t; if (vec_ok) { constexpr int V = 8; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } } \
-    else { set_error("bad dtype %d", (int)(dtype)); return UEGAN_E_INVALID; }                        \
-  } while (0)
-static inline int epc_of(int dtype) { return dtype == UEGAN_BF16 ? 8 : 4; }
 
 static int make_affine(Affine4& af, int C, const float* a, const float* b) {
   af.on = (a != nullptr);
@@ -409,12 +387,12 @@ static int make_affine(Affine4& af, int C, const float* a, const float* b) {
 extern "C" int uegan_nchw_to_nhwc(int dtype, const float* x, void* y, int B, int C, int Cp, int H, int W, const float* a, const float* b,
                                   uegan_stream_t stream) {
   UEGAN_CHECK_ARG(x && y && B > 0 && C > 0 && Cp >= C && H > 0 && W > 0, "bad args");
-  UEGAN_CHECK_ARG(Cp % (dtype == UEGAN_BF16 ? 8 : 4) == 0, "Cp must be a multiple of one 16-byte chunk");
+  UEGAN_CHECK_ARG(Cp % epc_of(dtype) == 0, "Cp must be a multiple of one 16-byte chunk");
   Affine4 af;
   int rc = make_affine(af, C, a, b);
   if (rc) return rc;
-  const size_t n = (size_t)B * Cp * H * W / (dtype == UEGAN_BF16 ? 8 : 4);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, (T*)y, B, C, Cp, H * W, af, 0));
+  const size_t n = (size_t)B * Cp * H * W / epc_of(dtype);
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, (T*)y, B, C, Cp, H * W, af, 0));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -439,7 +417,7 @@ extern "C" int uegan_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int
   int rc = make_affine(af, C, a, nullptr);
   if (rc) return rc;
   const size_t n = (size_t)B * C * H * W;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)x, y, B, C, Cp, H * W, af));
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)x, y, B, C, Cp, H * W, af));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -448,7 +426,7 @@ extern "C" int uegan_residual_clamp_fwd(int dtype, const void* res, const float*
                                         uegan_stream_t stream) {
   UEGAN_CHECK_ARG(res && x && out && Cp >= C, "bad args");
   const size_t n = (size_t)B * C * H * W;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((residual_clamp_fwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)res, x, out, B, C, Cp, H * W));
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((residual_clamp_fwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const T*)res, x, out, B, C, Cp, H * W));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -461,14 +439,14 @@ extern "C" int uegan_residual_clamp_bwd_act(int dtype, int act, const float* g, 
                                             int C, int Cp, int H, int W, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(g && res && x && dres && Cp >= C, "bad args");
   const size_t n = (size_t)B * Cp * H * W;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((residual_clamp_bwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, (const T*)res, x, (T*)dres, dx, B, C, Cp, H * W, act));
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((residual_clamp_bwd_kernel<T>), dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, (const T*)res, x, (T*)dres, dx, B, C, Cp, H * W, act));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 
 extern "C" int uegan_mul_fwd(int dtype, const void* a, const void* b, void* y, int64_t n, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(a && b && y && n > 0, "bad args");
-  DISPATCH_TV(dtype, n % epc_of(dtype) == 0, hipLaunchKernelGGL((mul_fwd_kernel<T, V>), dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)y, (size_t)n));
+  UEGAN_DISPATCH_TV(dtype, n % epc_of(dtype) == 0, hipLaunchKernelGGL((mul_fwd_kernel<T, V>), dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)y, (size_t)n));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -478,21 +456,21 @@ extern "C" int uegan_mul_bwd(int dtype, const void* g, const void* a, const void
 extern "C" int uegan_mul_bwd_act(int dtype, int act_a, int act_b, const void* g, const void* a, const void* b, void* da, void* db, int64_t n,
                                  uegan_stream_t stream) {
   UEGAN_CHECK_ARG(g && a && b && da && db && n > 0, "bad args");
-  DISPATCH_TV(dtype, n % epc_of(dtype) == 0, hipLaunchKernelGGL((mul_bwd_kernel<T, V>), dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (const T*)a, (const T*)b, (T*)da, (T*)db, (size_t)n, act_a, act_b));
+  UEGAN_DISPATCH_TV(dtype, n % epc_of(dtype) == 0, hipLaunchKernelGGL((mul_bwd_kernel<T, V>), dim3(grid_for((size_t)n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (const T*)a, (const T*)b, (T*)da, (T*)db, (size_t)n, act_a, act_b));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 extern "C" int uegan_upsample2x_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C > 0, "bad args");
   UEGAN_CHECK_ARG((long long)B * 2 * H <= 65535, "upsample2x: B * 2H rows exceed the grid's y extent");
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_fwd_kernel<T, V>), dim3(grid_for((size_t)2 * W * C / V, 64), B * 2 * H), dim3(row_threads((size_t)2 * W * C / V)), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_fwd_kernel<T, V>), dim3(grid_for((size_t)2 * W * C / V, 64), B * 2 * H), dim3(row_threads((size_t)2 * W * C / V)), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 extern "C" int uegan_upsample2x_bwd(int dtype, const void* gy, void* gx, int B, int H, int W, int C, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(gy && gx && B > 0 && H > 0 && W > 0 && C > 0, "bad args");
   UEGAN_CHECK_ARG((long long)B * H <= 65535, "upsample2x: B * H rows exceed the grid's y extent");
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_bwd_kernel<T, V>), dim3(grid_for((size_t)W * C / V, 64), B * H), dim3(row_threads((size_t)W * C / V)), 0, (hipStream_t)stream, (const T*)gy, (T*)gx, B, H, W, C));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_bwd_kernel<T, V>), dim3(grid_for((size_t)W * C / V, 64), B * H), dim3(row_threads((size_t)W * C / V)), 0, (hipStream_t)stream, (const T*)gy, (T*)gx, B, H, W, C));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -500,14 +478,14 @@ extern "C" int uegan_upsample2x_bwd(int dtype, const void* gy, void* gx, int B, 
 extern "C" int uegan_maxpool2x2_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(x && y && B > 0 && H > 1 && W > 1 && C > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2 needs even H,W");
   const size_t n = (size_t)B * (H / 2) * (W / 2) * C;
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_fwd_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_fwd_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 extern "C" int uegan_maxpool2x2_fwd_idx(int dtype, const void* x, void* y, void* idx, int B, int H, int W, int C, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(x && y && idx && B > 0 && H > 1 && W > 1 && C > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2 needs even H,W");
   const size_t n = (size_t)B * (H / 2) * (W / 2) * C;
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_fwd_idx_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, (unsigned char*)idx, B, H, W, C));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_fwd_idx_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, (unsigned char*)idx, B, H, W, C));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -515,7 +493,7 @@ extern "C" int uegan_maxpool2x2_bwd_idx(int dtype, int act, const void* y_pool, 
                                         uegan_stream_t stream) {
   UEGAN_CHECK_ARG(y_pool && idx && gy && gx && B > 0 && H > 1 && W > 1 && C > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2 needs even H,W");
   const size_t n = (size_t)B * (H / 2) * (W / 2) * C;
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_bwd_idx_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)y_pool, (const unsigned char*)idx, (const T*)gy, (T*)gx, B, H, W, C, act));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_bwd_idx_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)y_pool, (const unsigned char*)idx, (const T*)gy, (T*)gx, B, H, W, C, act));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
@@ -526,7 +504,7 @@ extern "C" int uegan_maxpool2x2_bwd_act(int dtype, int act, const void* x, const
                                         uegan_stream_t stream) {
   UEGAN_CHECK_ARG(x && gy && gx && B > 0 && H > 1 && W > 1 && C > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2 needs even H,W");
   const size_t n = (size_t)B * (H / 2) * (W / 2) * C;
-  DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, (T*)gx, B, H, W, C, act));
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T, V>), dim3(grid_for(n / V)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)gy, (T*)gx, B, H, W, C, act));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }

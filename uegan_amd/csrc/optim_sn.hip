@@ -3,6 +3,7 @@
 // forward, eps 1e-12, sigma = u^T W v, weight = weight_orig / sigma, u/v constants in backward;
 // torch.optim.Adam with weight_decay (L2 added to the gradient), trainer.py:337-338.
 #include "common.h"
+#include "launch.h"
 
 namespace uegan {
 
@@ -183,20 +184,26 @@ __global__ void rmsprop_kernel(const uegan_adam_tensor* desc, float lr, float al
 
 using namespace uegan;
 
-extern "C" int uegan_specnorm_grad(const float* g, const float* w, const float* u, const float* v, const float* sigma, float* dw, int rows,
-                                   int cols, float* tmp, uegan_stream_t stream) {
-  UEGAN_CHECK_ARG(g && w && u && v && sigma && dw && tmp && rows > 0 && cols > 0, "bad specnorm_grad args");
+// dw (+)= g - (<g, w> / sigma) * u v^T: the dot product as block partials, then the elementwise pass that folds them.
+// acc < 0: sig = {sigma, 1 / sigma} (uegan_specnorm_sigma's output), dw is overwritten; acc 0 / 1: sig = {1 / sigma}, dw = / +=
+static int specnorm_grad(const float* g, const float* w, const float* u, const float* v, const float* sig, float* dw, int rows, int cols,
+                         float* tmp, int acc, uegan_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)rows * cols;
-  int blocks = (int)((n + 1023) / 1024);
-  if (blocks > 512) blocks = 512;
-  if (blocks < 1) blocks = 1;
+  const int blocks = blocks_for(n, 1024, 512);
   const int nd = blocks < SN_DOTB ? blocks : SN_DOTB;
   hipLaunchKernelGGL(dot_kernel, dim3(nd), dim3(256), 0, s, g, w, tmp, n);
   UEGAN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sn_grad_kernel, dim3(blocks), dim3(256), 0, s, g, u, v, sigma, tmp, nd, dw, rows, cols);
+  if (acc < 0) hipLaunchKernelGGL(sn_grad_kernel, dim3(blocks), dim3(256), 0, s, g, u, v, sig, tmp, nd, dw, rows, cols);
+  else hipLaunchKernelGGL(sn_grad_acc_kernel, dim3(blocks), dim3(256), 0, s, g, u, v, sig, tmp, nd, dw, rows, cols, acc);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
+}
+
+extern "C" int uegan_specnorm_grad(const float* g, const float* w, const float* u, const float* v, const float* sigma, float* dw, int rows,
+                                   int cols, float* tmp, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(g && w && u && v && sigma && dw && tmp && rows > 0 && cols > 0, "bad specnorm_grad args");
+  return specnorm_grad(g, w, u, v, sigma, dw, rows, cols, tmp, -1, stream);
 }
 
 extern "C" size_t uegan_specnorm_grad_workspace_floats(void) { return SN_DOTB; }
@@ -248,26 +255,14 @@ extern "C" int uegan_specnorm_grad_acc(const float* g, const float* w, const flo
                                        int rows, int cols, float* tmp, int accumulate, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(g && w && u && v && inv_sigma && dw && tmp && rows > 0 && cols > 0, "bad specnorm_grad args");
   UEGAN_CHECK_ARG(!(accumulate && g == dw), "specnorm_grad_acc: accumulate needs g and dw in different buffers");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n = (size_t)rows * cols;
-  int blocks = (int)((n + 1023) / 1024);
-  if (blocks > 512) blocks = 512;
-  if (blocks < 1) blocks = 1;
-  const int nd = blocks < SN_DOTB ? blocks : SN_DOTB;
-  hipLaunchKernelGGL(dot_kernel, dim3(nd), dim3(256), 0, s, g, w, tmp, n);
-  UEGAN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sn_grad_acc_kernel, dim3(blocks), dim3(256), 0, s, g, u, v, inv_sigma, tmp, nd, dw, rows, cols, accumulate ? 1 : 0);
-  UEGAN_CHECK_LAUNCH();
-  return UEGAN_OK;
+  return specnorm_grad(g, w, u, v, inv_sigma, dw, rows, cols, tmp, accumulate ? 1 : 0, stream);
 }
 
 extern "C" int uegan_adam_l2_step(const uegan_adam_tensor* desc_dev, int n_tensors, int64_t max_n, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, float grad_scale, int step, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(desc_dev && n_tensors > 0 && max_n > 0 && step >= 1, "bad adam args");
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  int bx = (int)((max_n + 1023) / 1024);
-  if (bx > 128) bx = 128;
-  if (bx < 1) bx = 1;
+  const int bx = blocks_for((size_t)max_n, 1024, 128);
   hipLaunchKernelGGL(adam_kernel, dim3(bx, n_tensors), dim3(256), 0, (hipStream_t)stream, desc_dev, (float)(lr / bc1), beta1, beta2,
                      (float)(1.0 / sqrt(bc2)), eps, weight_decay, grad_scale);
   UEGAN_CHECK_LAUNCH();
@@ -277,9 +272,7 @@ extern "C" int uegan_adam_l2_step(const uegan_adam_tensor* desc_dev, int n_tenso
 extern "C" int uegan_rmsprop_step(const uegan_adam_tensor* desc_dev, int n_tensors, int64_t max_n, float lr, float alpha, float eps,
                                   float grad_scale, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(desc_dev && n_tensors > 0 && max_n > 0, "bad rmsprop args");
-  int bx = (int)((max_n + 1023) / 1024);
-  if (bx > 128) bx = 128;
-  if (bx < 1) bx = 1;
+  const int bx = blocks_for((size_t)max_n, 1024, 128);
   hipLaunchKernelGGL(rmsprop_kernel, dim3(bx, n_tensors), dim3(256), 0, (hipStream_t)stream, desc_dev, lr, alpha, eps, grad_scale);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;

@@ -1,5 +1,6 @@
 // Weight packing: OIHW fp32 master weights -> the OHWI / IHWO matrices of the storage format that the convolution kernels read.
 #include "conv_core.h"
+#include "launch.h"
 
 namespace uegan {
 
@@ -113,27 +114,17 @@ extern "C" int uegan_pack_weights_pair(int dtype, const float* w_oihw, int Cout,
   UEGAN_CHECK_ARG(dup_cin != 2 || dtype == UEGAN_BF16, "hi + lo pairs exist for the 16-bit storage format");
   const int Kp = (int)uegan_packed_k((int64_t)KH * KW * Cin_pad), Kp2 = (int)uegan_packed_k((int64_t)KH * KW * Cout_pad);
   const size_t total = (size_t)Cout_pad * Kp + (w_ihwo ? (size_t)Cin_pad * Kp2 : 0);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == UEGAN_F32)
-    hipLaunchKernelGGL((pack_weights_kernel<float>), dim3(blocks), dim3(256), 0, s, w_oihw, (float*)w_ohwi, (float*)w_ihwo, Cout, Cin, KH, KW,
-                       Cout_pad, Cin_pad, Kp, Kp2, Cin_total, (float*)nullptr, dup_cin);
-  else if (dtype == UEGAN_BF16)
-    hipLaunchKernelGGL((pack_weights_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, w_oihw, (bf16_t*)w_ohwi, (bf16_t*)w_ihwo, Cout, Cin, KH,
-                       KW, Cout_pad, Cin_pad, Kp, Kp2, Cin_total, (bf16_t*)w_ohwi_lo, dup_cin);
-  else
-    UEGAN_CHECK_ARG(false, "bad dtype");
+  // (w_ohwi_lo is null unless the storage type is the 16-bit one: checked above)
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((pack_weights_kernel<T>), dim3(grid_for(total, 2048)), dim3(256), 0, (hipStream_t)stream, w_oihw, (T*)w_ohwi, (T*)w_ihwo,
+                                              Cout, Cin, KH, KW, Cout_pad, Cin_pad, Kp, Kp2, Cin_total, (T*)w_ohwi_lo, dup_cin));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 
 extern "C" int uegan_pack_weights_multi(int dtype, const uegan_pack_entry* table_dev, int n_entries, int64_t total, uegan_stream_t stream) {
   UEGAN_CHECK_ARG(table_dev && n_entries > 0 && total > 0, "bad pack_weights_multi args");
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == UEGAN_F32) hipLaunchKernelGGL((pack_weights_multi_kernel<float>), dim3(blocks), dim3(256), 0, s, table_dev, n_entries, (long long)total);
-  else if (dtype == UEGAN_BF16) hipLaunchKernelGGL((pack_weights_multi_kernel<bf16_t>), dim3(blocks), dim3(256), 0, s, table_dev, n_entries, (long long)total);
-  else UEGAN_CHECK_ARG(false, "bad dtype");
+  UEGAN_DISPATCH_T(dtype, hipLaunchKernelGGL((pack_weights_multi_kernel<T>), dim3(grid_for((size_t)total, 4096)), dim3(256), 0, (hipStream_t)stream, table_dev,
+                                              n_entries, (long long)total));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
