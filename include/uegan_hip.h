@@ -322,6 +322,12 @@ int uegan_mul_bwd_act(int dtype, int act_a, int act_b, const void* g, const void
 /* bilinear x2, align_corners=True (models.py:191-201) and its adjoint */
 int uegan_upsample2x_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C, uegan_stream_t stream);
 int uegan_upsample2x_bwd(int dtype, const void* gy, void* gx, int B, int H, int W, int C, uegan_stream_t stream);
+/* The forward on a TILE of a larger map (tiled inference; no adjoint): x is the [B][H][W][C] tile at origin (oy, ox) of a global GH x GW map, y
+ * [B][2H][2W][C] rows [2 oy, 2 oy + 2H) and columns [2 ox, 2 ox + 2W) of the global x2 result.  Source indices and weights are those of the GLOBAL
+ * output index (the align_corners scale (GH - 1) / (2 GH - 1)), shifted by the origin and clamped into the tile; a clamped source is only ever asked
+ * for within one sample of a tile edge that is not a map edge -- inside the halo the caller discards.  oy = ox = 0, GH = H, GW = W is
+ * uegan_upsample2x_fwd bit for bit. */
+int uegan_upsample2x_fwd_at(int dtype, const void* x, void* y, int B, int H, int W, int C, int oy, int ox, int GH, int GW, uegan_stream_t stream);
 /* MaxPool2d(2,2) (torchvision VGG features idx 4,9,18,27) and backward (first max in scan order) */
 int uegan_maxpool2x2_fwd(int dtype, const void* x, void* y, int B, int H, int W, int C, uegan_stream_t stream);
 int uegan_maxpool2x2_bwd(int dtype, const void* x, const void* gy, void* gx, int B, int H, int W, int C,
@@ -355,6 +361,12 @@ int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int 
  * quantisation: what native-size inference writes after the generator ran on the image extended to multiples of 16. */
 int uegan_montage_crop_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
                           uegan_stream_t stream);
+/* uegan_montage_crop_u8 with a window origin and a destination: the H x W window at (sy, sx) of source k is quantised into rows [dy, dy + H) and
+ * columns [dx + k*Wpanel, dx + k*Wpanel + W) of the larger image y[B][Hd][Wd][C] (Wpanel >= W); no other byte of y is written.  Tiled native-size
+ * inference writes every tile's core straight into the full-size result this way.  sy = sx = dy = dx = 0, Hd = H, Wd = n*W, Wpanel = W is
+ * uegan_montage_crop_u8. */
+int uegan_montage_place_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int sy, int sx, int H, int W,
+                           int Hd, int Wd, int dy, int dx, int Wpanel, uegan_stream_t stream);
 /* Per image b < B of two uint8 NHWC stacks, after cropping crop_border pixels on every side (CalcPSNR.py:24,56 / CalcSSIM.py:24,56):
  *   sqdiff_sum[b] (may be NULL) = sum (a - b)^2               -> PSNR = 10 log10(255^2 / (sqdiff_sum / n)), CalcPSNR.py:85-92
  *   ssim_sum[b]   (may be NULL) = sum over channels and valid 7x7 windows of the SSIM index with skimage's defaults as called at
@@ -462,6 +474,19 @@ int uegan_gam_bwd(int dtype, const void* g, const void* y, const void* x, const 
  *   uegan_affine_act_bwd_apply gx = g * ca[b,c] + x * cb[b,c] + cc[b,c]                  (ca / cb / cc NULL: 1 / 0 / 0)
  * act: any UEGAN_ACT_* (evaluated on the pre-activation, which is recomputed from x and never stored). */
 int uegan_moments(int dtype, const void* x, float* mean, float* var, float* tmp, int B, int HW, int C, uegan_stream_t stream);
+/* Moments of a map that is only ever seen tile by tile (tiled inference: the attention modules normalise with whole-image moments).
+ *   uegan_moments_window_acc  sum[b*C + c] += sum of z, sumsq[b*C + c] += sum of z^2 over rows [y0, y1) x columns [x0, x1) of the NHWC map x
+ *                             [B][H][W][C], read in place through its row pitch; x_lo (may be NULL; 16-bit storage): z = x + x_lo, a hi + lo pair.
+ *                             The accumulators are DOUBLE [B*C], zeroed by the caller before the first window.  Partials are combined in a fixed
+ *                             order without atomics: the same windows in the same order give the same bits.
+ *                             tmp: uegan_moments_window_workspace_bytes(B, C) bytes, 8-byte aligned.
+ *   uegan_moments_finish      mean[i] = sum[i] / count, rstd[i] = 1 / sqrt(sumsq[i] / count - mean^2 + eps) for i < n (= B*C): biased variance,
+ *                             evaluated in double (eps < 0: the variance itself, as uegan_conv2d_fwd_stats) -- the [2][B][C] layout InstanceNorm takes
+ *                             (uegan_instnorm_apply). */
+size_t uegan_moments_window_workspace_bytes(int B, int C);
+int uegan_moments_window_acc(int dtype, const void* x, const void* x_lo, int B, int H, int W, int C, int y0, int y1, int x0, int x1, double* sum,
+                             double* sumsq, void* tmp, uegan_stream_t stream);
+int uegan_moments_finish(const double* sum, const double* sumsq, double count, float eps, float* mean, float* rstd, int n, uegan_stream_t stream);
 int uegan_affine_act_fwd(int dtype, int act, const void* x, const float* scale, const float* shift, void* y, int B, int HW, int C,
                          uegan_stream_t stream);
 int uegan_affine_act_bwd_sums(int dtype, int act, const void* gy, const void* x, const float* scale, const float* shift, float* sums,

@@ -106,6 +106,7 @@ SIGNATURES = {
     "uegan_mul_fwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "uegan_mul_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "uegan_upsample2x_fwd": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "uegan_upsample2x_fwd_at": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_upsample2x_bwd": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_maxpool2x2_fwd": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_maxpool2x2_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
@@ -116,6 +117,9 @@ SIGNATURES = {
     "uegan_gam_bwd_ws_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "uegan_gam_bwd": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_sz, c_int, c_int, c_int, c_vp]),
     "uegan_moments": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    "uegan_moments_window_workspace_bytes": (c_sz, [c_int, c_int]),
+    "uegan_moments_window_acc": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "uegan_moments_finish": (c_int, [c_vp, c_vp, C.c_double, c_f32, c_vp, c_vp, c_int, c_vp]),
     "uegan_affine_act_fwd": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "uegan_affine_act_bwd_sums": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "uegan_affine_act_bwd_apply": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
@@ -156,6 +160,7 @@ SIGNATURES = {
     "uegan_quantize_u8": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_montage_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_montage_crop_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "uegan_montage_place_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int] + [c_int] * 11 + [c_vp]),
     "uegan_native_input": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),

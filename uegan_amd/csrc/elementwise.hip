@@ -163,6 +163,43 @@ __global__ void upsample2x_fwd_kernel(const T* x, T* y, int B, int H, int W, int
   }
 }
 
+__device__ __forceinline__ int clamp_idx(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
+// the same for a TILE of a larger map: x is the [H][W] tile at origin (ty, tx) of a global [GH][GW] map, y rows [2 ty, 2 ty + 2H) and columns
+// [2 tx, 2 tx + 2W) of the GLOBAL x2 result.  Source indices and weights come from the global output index (bilinear_src on (GH, 2 GH): the sampling phase
+// of align_corners depends on the whole map's size), are shifted by the origin and clamped into the tile -- a source the tile does not hold is only ever
+// asked for by an output inside the tile's halo, which the caller discards.  ty = tx = 0, GH = H, GW = W: upsample2x_fwd_kernel bit for bit.
+template <typename T, int V>
+__global__ void upsample2x_fwd_at_kernel(const T* x, T* y, int B, int H, int W, int C, int ty, int tx, int GH, int GW) {
+  const int OH = 2 * H, OW = 2 * W, CV = C / V;
+  const int row = blockIdx.y, b = row / OH, oy = row - b * OH;
+  int y0, y1;
+  float ly;
+  bilinear_src(2 * ty + oy, GH, 2 * GH, y0, y1, ly);
+  y0 = clamp_idx(y0 - ty, H);
+  y1 = clamp_idx(y1 - ty, H);
+  const float hy = 1.f - ly;
+  const T* r0 = x + ((size_t)b * H + y0) * W * C;
+  const T* r1 = x + ((size_t)b * H + y1) * W * C;
+  T* yo = y + (size_t)row * OW * C;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < OW * CV; i += gridDim.x * blockDim.x) {
+    const int ox = i / CV, c = (i - ox * CV) * V;
+    int x0, x1;
+    float lx;
+    bilinear_src(2 * tx + ox, GW, 2 * GW, x0, x1, lx);
+    x0 = clamp_idx(x0 - tx, W);
+    x1 = clamp_idx(x1 - tx, W);
+    float v00[V], v01[V], v10[V], v11[V];
+    Vec<T, V>::ld(r0 + (size_t)x0 * C + c, v00);
+    Vec<T, V>::ld(r0 + (size_t)x1 * C + c, v01);
+    Vec<T, V>::ld(r1 + (size_t)x0 * C + c, v10);
+    Vec<T, V>::ld(r1 + (size_t)x1 * C + c, v11);
+    const float hx = 1.f - lx;
+#pragma unroll
+    for (int e = 0; e < V; ++e) v00[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+    Vec<T, V>::st(yo + (size_t)ox * C + c, v00);
+  }
+}
+
 // adjoint of the above in gather form: every input pixel scans the <=6 output rows/cols that can touch it; blockIdx.y = (image, input
 // row): the live output rows and their weights are block-uniform
 template <typename T, int V>
@@ -464,6 +501,15 @@ extern "C" int uegan_upsample2x_fwd(int dtype, const void* x, void* y, int B, in
   UEGAN_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C > 0, "bad args");
   UEGAN_CHECK_ARG((long long)B * 2 * H <= 65535, "upsample2x: B * 2H rows exceed the grid's y extent");
   UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_fwd_kernel<T, V>), dim3(grid_for((size_t)2 * W * C / V, 64), B * 2 * H), dim3(row_threads((size_t)2 * W * C / V)), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C));
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+extern "C" int uegan_upsample2x_fwd_at(int dtype, const void* x, void* y, int B, int H, int W, int C, int oy, int ox, int GH, int GW, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C > 0, "bad args");
+  UEGAN_CHECK_ARG(oy >= 0 && ox >= 0 && oy + H <= GH && ox + W <= GW && GH <= (1 << 24) && GW <= (1 << 24),
+                  "upsample2x_at: the %d x %d tile at (%d, %d) does not lie inside its %d x %d map", H, W, oy, ox, GH, GW);
+  UEGAN_CHECK_ARG((long long)B * 2 * H <= 65535, "upsample2x: B * 2H rows exceed the grid's y extent");
+  UEGAN_DISPATCH_TV(dtype, C % epc_of(dtype) == 0, hipLaunchKernelGGL((upsample2x_fwd_at_kernel<T, V>), dim3(grid_for((size_t)2 * W * C / V, 64), B * 2 * H), dim3(row_threads((size_t)2 * W * C / V)), 0, (hipStream_t)stream, (const T*)x, (T*)y, B, H, W, C, oy, ox, GH, GW));
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }

@@ -46,13 +46,21 @@ __global__ void quantize_u8_kernel(const float* x, uint8_t* y, int B, int C, int
 // ---- up to four [-1,1] NCHW fp32 images side by side -> ONE uint8 NHWC image [B][H][n*W][C], panel k in columns [k*W, (k+1)*W): what
 // save_image(torch.cat([denorm(a), denorm(b), ...], 3)) writes (trainer.py:182-183,244-245, tester.py:73-74), with quantize_u8_kernel's
 // arithmetic.  The source pointers travel by value, like CopyTable.  HBM-bound: 4 B read + 1 B written per element, each exactly once.
-// The sources are [B][C][Hs][Ws] planes of which the top-left H x W window is taken (uegan_montage_crop_u8; uegan_montage_u8: Hs = H, Ws = W). ----
+// The sources are [B][C][Hs][Ws] planes of which the H x W window at (sy, sx) is taken; panel k goes to rows [dy, dy + H) and columns
+// [dx + k*Wp, dx + k*Wp + W) of a [B][Hd][Wd][C] image of which nothing else is written (MontageGeom).  uegan_montage_place_u8 sets all of it (tiled
+// inference writes each tile's core into the full-size result); uegan_montage_crop_u8: window and destination at the origin, Hd = H, Wd = n*W, Wp = W;
+// uegan_montage_u8: also Hs = H, Ws = W. ----
 constexpr int MONTAGE_MAX_SRCS = 4;
 constexpr int MONTAGE_THREADS = 256;
 constexpr int MONTAGE_MAX_BLOCKS = 1024;      // grid cap: 4 blocks (16 waves) per CU on 256 CUs, the rest by grid stride
 constexpr int MONTAGE_VEC = 4;                // pixels per thread of the vector path (uegan_amd/tester.py mirrors these three numbers)
 struct MontageSrcs {
   const float* p[MONTAGE_MAX_SRCS];
+};
+struct MontageGeom {
+  int Hs, Ws, sy, sx;      // source planes, window origin
+  int H, W;                // window
+  int Hd, Wd, dy, dx, Wp;  // destination image, origin of panel 0, panel pitch in columns
 };
 
 __device__ __forceinline__ uint32_t quantize_u8(float x) {
@@ -63,10 +71,11 @@ __device__ __forceinline__ uint32_t quantize_u8(float x) {
   return (uint32_t)(uint8_t)v;                 // truncation, like Tensor.to(torch.uint8)
 }
 
-// vector path (W % 4 == 0, Ws % 4 == 0, sources 16-byte and y 4-byte aligned): one thread = 4 neighbouring pixels of one panel row: one 16-byte load per
+// vector path (W, Ws, sx, and for C = 3 also Wd, dx, Wp multiples of 4; sources 16-byte and y 4-byte aligned): one thread = 4 neighbouring pixels of one panel row: one 16-byte load per
 // plane (a wave reads 1 KiB of a plane row in one instruction), C whole dwords stored (4 * C bytes: the 4 pixels' bytes are contiguous in NHWC)
 template <int C>
-__global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int Hs, int Ws, int H, int W) {
+__global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, MontageGeom g) {
+  const int Hs = g.Hs, Ws = g.Ws, H = g.H, W = g.W;
   const int wq = W / MONTAGE_VEC;
   const size_t items = rows * n * wq;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
@@ -75,7 +84,7 @@ __global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t r
     const int k = (int)(t % n);
     const size_t row = t / n;                  // b * H + h
     const size_t b = row / H, h = row - b * H;
-    const float* src = s.p[k] + ((b * C) * Hs + h) * Ws + (size_t)q * MONTAGE_VEC;
+    const float* src = s.p[k] + ((b * C) * Hs + g.sy + h) * Ws + g.sx + (size_t)q * MONTAGE_VEC;
     uint32_t by[MONTAGE_VEC * C];              // byte j of the 4 * C output bytes = pixel j / C, channel j % C
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -85,14 +94,15 @@ __global__ void montage_u8_vec_kernel(MontageSrcs s, int n, uint8_t* y, size_t r
       by[2 * C + c] = quantize_u8(v[2]);
       by[3 * C + c] = quantize_u8(v[3]);
     }
-    uint32_t* dst = reinterpret_cast<uint32_t*>(y + ((row * n + k) * W + (size_t)q * MONTAGE_VEC) * C);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(y + (((b * g.Hd + g.dy + h) * g.Wd) + g.dx + (size_t)k * g.Wp + (size_t)q * MONTAGE_VEC) * C);
 #pragma unroll
     for (int d = 0; d < C; ++d) dst[d] = by[4 * d] | (by[4 * d + 1] << 8) | (by[4 * d + 2] << 16) | (by[4 * d + 3] << 24);
   }
 }
 
 // scalar path (any width, any alignment, any C): one thread = one output pixel
-__global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int C, int Hs, int Ws, int H, int W) {
+__global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows, int C, MontageGeom g) {
+  const int Hs = g.Hs, Ws = g.Ws, H = g.H, W = g.W;
   const size_t items = rows * n * W;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
     const int w = (int)(i % W);
@@ -100,8 +110,9 @@ __global__ void montage_u8_kernel(MontageSrcs s, int n, uint8_t* y, size_t rows,
     const int k = (int)(t % n);
     const size_t row = t / n;
     const size_t b = row / H, h = row - b * H;
-    const float* src = s.p[k] + ((b * C) * Hs + h) * Ws + w;
-    for (int c = 0; c < C; ++c) y[i * C + c] = (uint8_t)quantize_u8(src[(size_t)c * Hs * Ws]);
+    const float* src = s.p[k] + ((b * C) * Hs + g.sy + h) * Ws + g.sx + w;
+    uint8_t* dst = y + (((b * g.Hd + g.dy + h) * g.Wd) + g.dx + (size_t)k * g.Wp + w) * C;
+    for (int c = 0; c < C; ++c) dst[c] = (uint8_t)quantize_u8(src[(size_t)c * Hs * Ws]);
   }
 }
 
@@ -282,13 +293,18 @@ extern "C" int uegan_quantize_u8(const float* x_nchw, uint8_t* y_nhwc, int B, in
   return UEGAN_OK;
 }
 
-static int montage_launch(const char* who, const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
-                          uegan_stream_t stream) {
+static int montage_launch(const char* who, const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, const MontageGeom& g, uegan_stream_t stream) {
+  const int Hs = g.Hs, Ws = g.Ws, H = g.H, W = g.W;
   UEGAN_CHECK_ARG(srcs_nchw && y_nhwc && B > 0 && C > 0 && H > 0 && W > 0, "bad %s args", who);
-  UEGAN_CHECK_ARG(H <= Hs && W <= Ws, "%s: the %d x %d window does not fit its %d x %d source", who, H, W, Hs, Ws);
   UEGAN_CHECK_ARG(n >= 1 && n <= MONTAGE_MAX_SRCS, "%s takes 1..%d images (got %d)", who, MONTAGE_MAX_SRCS, n);
+  UEGAN_CHECK_ARG(g.sy >= 0 && g.sx >= 0 && (long long)g.sy + H <= Hs && (long long)g.sx + W <= Ws, "%s: the %d x %d window at (%d, %d) does not fit its %d x %d source",
+                  who, H, W, g.sy, g.sx, Hs, Ws);
+  UEGAN_CHECK_ARG(g.dy >= 0 && g.dx >= 0 && g.Wp >= W && (long long)g.dy + H <= g.Hd && (long long)g.dx + (long long)(n - 1) * g.Wp + W <= g.Wd,
+                  "%s: %d panels of %d x %d (pitch %d) at (%d, %d) do not fit the %d x %d destination", who, n, H, W, g.Wp, g.dy, g.dx, g.Hd, g.Wd);
   MontageSrcs s;
-  bool vec = W % MONTAGE_VEC == 0 && Ws % MONTAGE_VEC == 0 && (uintptr_t)y_nhwc % 4 == 0 && (C == 1 || C == 3 || C == 4);
+  bool vec = W % MONTAGE_VEC == 0 && Ws % MONTAGE_VEC == 0 && g.sx % MONTAGE_VEC == 0 && (uintptr_t)y_nhwc % 4 == 0 && (C == 1 || C == 3 || C == 4);
+  // (every panel row starts on a dword of y: (Wd, dx, Wp) * C bytes are multiples of 4)
+  vec = vec && ((size_t)g.Wd * C) % 4 == 0 && ((size_t)g.dx * C) % 4 == 0 && (n == 1 || ((size_t)g.Wp * C) % 4 == 0);
   for (int k = 0; k < MONTAGE_MAX_SRCS; ++k) {
     s.p[k] = k < n ? srcs_nchw[k] : nullptr;
     if (k < n) {
@@ -301,21 +317,26 @@ static int montage_launch(const char* who, const float* const* srcs_nchw, int n,
   const size_t want = (items + MONTAGE_THREADS - 1) / MONTAGE_THREADS;
   const dim3 grid((unsigned)(want < (size_t)MONTAGE_MAX_BLOCKS ? want : (size_t)MONTAGE_MAX_BLOCKS)), block(MONTAGE_THREADS);
   hipStream_t st = (hipStream_t)stream;
-  if (!vec) hipLaunchKernelGGL(montage_u8_kernel, grid, block, 0, st, s, n, y_nhwc, rows, C, Hs, Ws, H, W);
-  else if (C == 3) hipLaunchKernelGGL((montage_u8_vec_kernel<3>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
-  else if (C == 1) hipLaunchKernelGGL((montage_u8_vec_kernel<1>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
-  else hipLaunchKernelGGL((montage_u8_vec_kernel<4>), grid, block, 0, st, s, n, y_nhwc, rows, Hs, Ws, H, W);
+  if (!vec) hipLaunchKernelGGL(montage_u8_kernel, grid, block, 0, st, s, n, y_nhwc, rows, C, g);
+  else if (C == 3) hipLaunchKernelGGL((montage_u8_vec_kernel<3>), grid, block, 0, st, s, n, y_nhwc, rows, g);
+  else if (C == 1) hipLaunchKernelGGL((montage_u8_vec_kernel<1>), grid, block, 0, st, s, n, y_nhwc, rows, g);
+  else hipLaunchKernelGGL((montage_u8_vec_kernel<4>), grid, block, 0, st, s, n, y_nhwc, rows, g);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }
 
 extern "C" int uegan_montage_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int H, int W, uegan_stream_t stream) {
-  return montage_launch("montage_u8", srcs_nchw, n, y_nhwc, B, C, H, W, H, W, stream);
+  return montage_launch("montage_u8", srcs_nchw, n, y_nhwc, B, C, MontageGeom{H, W, 0, 0, H, W, H, n * W, 0, 0, W}, stream);
 }
 
 extern "C" int uegan_montage_crop_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int H, int W,
                                      uegan_stream_t stream) {
-  return montage_launch("montage_crop_u8", srcs_nchw, n, y_nhwc, B, C, Hs, Ws, H, W, stream);
+  return montage_launch("montage_crop_u8", srcs_nchw, n, y_nhwc, B, C, MontageGeom{Hs, Ws, 0, 0, H, W, H, n * W, 0, 0, W}, stream);
+}
+
+extern "C" int uegan_montage_place_u8(const float* const* srcs_nchw, int n, uint8_t* y_nhwc, int B, int C, int Hs, int Ws, int sy, int sx, int H, int W,
+                                      int Hd, int Wd, int dy, int dx, int Wpanel, uegan_stream_t stream) {
+  return montage_launch("montage_place_u8", srcs_nchw, n, y_nhwc, B, C, MontageGeom{Hs, Ws, sy, sx, H, W, Hd, Wd, dy, dx, Wpanel}, stream);
 }
 
 extern "C" int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, double* sqdiff_sum, double* ssim_sum, int B, int H, int W,

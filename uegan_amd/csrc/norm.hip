@@ -2,7 +2,8 @@
 // (non-affine) forward and backward, affine normalisation + activation on explicit coefficients, and the fidelity-loss tap
 // weight * MSE(IN(x), IN(y)) with its gradient.  All HBM-bound: per-thread fp32 accumulation, an LDS tree over the block's pixel lanes,
 // fp32 partials per pixel split combined by a finalize kernel -- moments with Chan's formula (means / M2), so the variance never suffers
-// E[x^2]-E[x]^2 cancellation.  The adversarial and reconstruction losses are in loss.hip.
+// E[x^2]-E[x]^2 cancellation.  The adversarial and reconstruction losses are in loss.hip.  Tiled inference adds the moments over a WINDOW of a map,
+// accumulated in double across calls (WinPlan, further down).
 //
 // Reference arithmetic: nn.InstanceNorm2d(affine=False) (models.py:227,236; losses.py:18,30-34), the norm_fun / act_fun variants of ConvBlock
 // (models.py:88-101, 249-281), PerceptualLoss tap term (losses.py:30-34).
@@ -472,6 +473,114 @@ __global__ void percep_grad_kernel(const T* x, const T* y, const float* st, cons
   }
 }
 
+// ----------------------------------------------------------------------------------------------------
+// Moments over a WINDOW of an NHWC map, accumulated across calls: tiled inference collects the attention modules' whole-image moments tile by tile
+// (each tile contributes the window it owns).  Per (image, channel) the running sum z and sum z^2 live in DOUBLE: z and z^2 are exact there (24-bit
+// significands), so the sums carry ~n * 2^-53 relative error and E[z^2] - E[z]^2 loses nothing that matters against the fp32 one-pass moments above.
+// Same thread layout as RedPlan (CG channel lanes x PL pixel lanes, V channels per thread); a block owns one of S splits of the window's pixels,
+// which it reads in place through the map's row pitch.  No atomics: window_fold_kernel adds the S partials of a (b, c) in split order.
+// ----------------------------------------------------------------------------------------------------
+constexpr int WINDOW_MAX_SPLITS = 512;      // grid cap in x; the workspace is sized by it (uegan_moments_window_workspace_bytes)
+constexpr int WINDOW_PIX_PER_LANE = 4;      // a split is at least this many pixels per pixel lane
+struct WinPlan {
+  int B, H, W, C;
+  int y0, x0, wh, ww;      // window origin and extent
+  int V, CG, PL, ncg;      // as RedPlan
+  int S, chunk;            // pixel splits of the wh * ww window pixels, pixels per split
+  dim3 grid() const { return dim3(S, ncg, B); }
+};
+static WinPlan make_win_plan(int B, int H, int W, int C, int y0, int y1, int x0, int x1, int dtype, bool aligned) {
+  const int epc = epc_of(dtype);
+  WinPlan p;
+  p.B = B; p.H = H; p.W = W; p.C = C; p.y0 = y0; p.x0 = x0; p.wh = y1 - y0; p.ww = x1 - x0;
+  p.V = (C % epc == 0 && aligned) ? epc : 1;
+  const int lanes = C / p.V;
+  int cg = 1;
+  while (cg < lanes && cg < 64) cg <<= 1;
+  p.CG = cg;
+  p.PL = 256 / cg;
+  p.ncg = (lanes + cg - 1) / cg;
+  const size_t n = (size_t)p.wh * p.ww;
+  const int s = blocks_for(n, WINDOW_PIX_PER_LANE * p.PL, WINDOW_MAX_SPLITS);
+  p.chunk = (int)((n + s - 1) / s);
+  p.S = (int)((n + p.chunk - 1) / p.chunk);
+  return p;
+}
+
+// part[((b*S + s)*C + c)*2 + {0,1}] = {sum z, sum z^2} over split s of the window;  PAIR: z = x + x_lo (a hi + lo pair of 16-bit planes)
+template <typename T, int V, bool PAIR>
+__global__ void window_partial_kernel(const T* x, const T* xl, double* part, WinPlan p) {
+  __shared__ double sh[2][V][256];
+  const int s = blockIdx.x, cg = blockIdx.y, b = blockIdx.z;
+  const int cl = threadIdx.x % p.CG, pl = threadIdx.x / p.CG;
+  const int c0 = (cg * p.CG + cl) * V;
+  const bool cvalid = c0 < p.C;
+  const int n = p.wh * p.ww, q0 = s * p.chunk;
+  const int q1 = q0 + p.chunk < n ? q0 + p.chunk : n;
+  double a0[V], a1[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) { a0[e] = 0.0; a1[e] = 0.0; }
+  if (cvalid) {
+    for (int q = q0 + pl; q < q1; q += p.PL) {
+      const int r = q / p.ww, col = q - r * p.ww;
+      const size_t o = (((size_t)b * p.H + p.y0 + r) * p.W + p.x0 + col) * p.C + c0;
+      float v[V];
+      Vec<T, V>::ld(x + o, v);
+      if (PAIR) {
+        float l[V];
+        Vec<T, V>::ld(xl + o, l);
+#pragma unroll
+        for (int e = 0; e < V; ++e) { const double z = (double)v[e] + (double)l[e]; a0[e] += z; a1[e] += z * z; }
+      } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) { const double z = (double)v[e]; a0[e] += z; a1[e] += z * z; }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) { sh[0][e][threadIdx.x] = a0[e]; sh[1][e][threadIdx.x] = a1[e]; }
+  __syncthreads();
+  for (int half = p.PL >> 1; half > 0; half >>= 1) {        // tree over the pixel lanes (PL is a power of two): a fixed order
+    if (pl < half) {
+      const int o = threadIdx.x + half * p.CG;
+#pragma unroll
+      for (int e = 0; e < V; ++e) { sh[0][e][threadIdx.x] += sh[0][e][o]; sh[1][e][threadIdx.x] += sh[1][e][o]; }
+    }
+    __syncthreads();
+  }
+  if (pl == 0 && cvalid) {
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      double* o = part + (((size_t)b * p.S + s) * p.C + c0 + e) * 2;
+      o[0] = sh[0][e][threadIdx.x]; o[1] = sh[1][e][threadIdx.x];
+    }
+  }
+}
+// sum[b*C + c] += the S partials of (b, c) in split order, sumsq likewise: one thread per (b, c)
+__global__ void window_fold_kernel(const double* part, double* sum, double* sumsq, int B, int S, int C) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * C) return;
+  const int b = i / C, c = i - b * C;
+  double t0 = 0.0, t1 = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const double* o = part + (((size_t)b * S + s) * C + c) * 2;
+    t0 += o[0];
+    t1 += o[1];
+  }
+  sum[i] += t0;
+  sumsq[i] += t1;
+}
+// accumulators -> mean, rstd = 1 / sqrt(var + eps) (biased variance; eps < 0: the variance itself), evaluated in double and rounded once
+__global__ void window_finish_kernel(const double* sum, const double* sumsq, double count, float eps, float* mean, float* rstd, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double m = sum[i] / count;
+  double var = sumsq[i] / count - m * m;
+  if (var < 0.0) var = 0.0;
+  mean[i] = (float)m;
+  rstd[i] = eps < 0.f ? (float)var : (float)(1.0 / sqrt(var + (double)eps));
+}
+
 }  // namespace uegan
 
 using namespace uegan;
@@ -561,6 +670,37 @@ extern "C" int uegan_moments(int dtype, const void* x, float* mean, float* var, 
   hipStream_t s = (hipStream_t)stream;
   RED_LAUNCH((moments_partial_kernel<T, V>), dtype, p, s, (const T*)x, tmp, p);
   return finalize_moments(p, tmp, mean, var, -1.f, s);
+}
+
+extern "C" size_t uegan_moments_window_workspace_bytes(int B, int C) {
+  return (size_t)(B > 0 ? B : 0) * (size_t)(C > 0 ? C : 0) * WINDOW_MAX_SPLITS * 2 * sizeof(double);
+}
+
+extern "C" int uegan_moments_window_acc(int dtype, const void* x, const void* x_lo, int B, int H, int W, int C, int y0, int y1, int x0, int x1,
+                                        double* sum, double* sumsq, void* tmp, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(x && sum && sumsq && tmp && B > 0 && H > 0 && W > 0 && C > 0, "bad moments_window args");
+  UEGAN_CHECK_ARG(0 <= y0 && y0 < y1 && y1 <= H && 0 <= x0 && x0 < x1 && x1 <= W, "moments_window: rows [%d, %d) x columns [%d, %d) is no window of a %d x %d map",
+                  y0, y1, x0, x1, H, W);
+  UEGAN_CHECK_ARG((long long)(y1 - y0) * (x1 - x0) < (1LL << 31) - 1024 && B <= 65535, "moments_window: window too large");
+  UEGAN_CHECK_ARG(!x_lo || dtype == UEGAN_BF16, "hi + lo pairs exist for the 16-bit storage format");
+  UEGAN_CHECK_ARG((uintptr_t)tmp % 8 == 0 && (uintptr_t)sum % 8 == 0 && (uintptr_t)sumsq % 8 == 0, "moments_window: 8-byte alignment");
+  const bool aligned = (uintptr_t)x % 16 == 0 && (uintptr_t)x_lo % 16 == 0;
+  const WinPlan p = make_win_plan(B, H, W, C, y0, y1, x0, x1, dtype, aligned);
+  hipStream_t s = (hipStream_t)stream;
+  double* part = (double*)tmp;
+  UEGAN_DISPATCH_BOOL(x_lo != nullptr, PAIR, UEGAN_DISPATCH_TV(dtype, p.V != 1,
+      hipLaunchKernelGGL((window_partial_kernel<T, V, PAIR>), p.grid(), dim3(256), 0, s, (const T*)x, (const T*)x_lo, part, p)));
+  UEGAN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(window_fold_kernel, dim3(grid_for((size_t)B * C)), dim3(256), 0, s, part, sum, sumsq, B, p.S, C);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_moments_finish(const double* sum, const double* sumsq, double count, float eps, float* mean, float* rstd, int n, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(sum && sumsq && mean && rstd && n > 0 && count >= 1.0, "bad moments_finish args");
+  hipLaunchKernelGGL(window_finish_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, (hipStream_t)stream, sum, sumsq, count, eps, mean, rstd, n);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
 }
 
 extern "C" int uegan_affine_act_fwd(int dtype, int act, const void* x, const float* scale, const float* shift, void* y, int B, int HW, int C,

@@ -115,6 +115,14 @@ NATIVE_MIN_SIDE = 32
 # per-image cap of the padded area.  8 * 1024^2 is the per-launch element count the suite has run the generator at (8 x 3 x 1024^2): a statement
 # of what has been exercised, not a measured limit
 NATIVE_MAX_PIXELS = 8 * 1024 * 1024
+# Above the cap an image is enhanced tile by tile (tester.enhance_native(tile=)): cores of NATIVE_TILE pixels a side, each run with a
+# halo -- the receptive-field radius of the network behind the point where the tiles are joined, rounded up to the stride-16 grid: 67 -> 80 input
+# pixels for the whole generator (pass 2), 18 -> 32 for the encoder (pass 1, which collects the attention modules' whole-image moments).
+NATIVE_TILE = 1024
+NATIVE_TILE_HALO = 80
+NATIVE_TILE_HALO_ENC = 32
+# the largest image tools/bench_tiled.py has run on the GPU (4096 x 6144, profiles/tiled_bench.json): as above, what has been exercised
+NATIVE_TILED_MAX_PIXELS = 4096 * 6144
 # the launcher's constants (csrc/input.hip: NATIVE_MAX_BLOCKS, NATIVE_THREADS, NATIVE_VEC): above MAX_BLOCKS * THREADS groups of VEC output
 # pixels the kernel loops by grid stride -- tests/test_native.py crosses the threshold on both read paths
 NATIVE_MAX_BLOCKS, NATIVE_THREADS, NATIVE_VEC = 2048, 256, 4
@@ -135,6 +143,38 @@ def check_native_size(h, w):
         raise ValueError("native-size inference: %d x %d pads to %d x %d = %d pixels, above the %d this package has been exercised at"
                          % (h, w, hp, wp, hp * wp, NATIVE_MAX_PIXELS))
     return hp, wp
+
+
+def check_native_tile(core):
+    """raise ValueError unless `core` is a usable tile core: a multiple of 16, at least 32"""
+    if int(core) != core or core % NATIVE_MULTIPLE or core < NATIVE_MIN_SIDE:
+        raise ValueError("tiled native-size inference needs a tile core that is a multiple of %d and at least %d (got %r)"
+                         % (NATIVE_MULTIPLE, NATIVE_MIN_SIDE, core))
+    return int(core)
+
+
+def check_native_tiled_size(h, w):
+    """check_native_size for an image that is enhanced tile by tile: both sides >= 32, padded area <= NATIVE_TILED_MAX_PIXELS.  Returns (hp, wp)."""
+    if h < NATIVE_MIN_SIDE or w < NATIVE_MIN_SIDE:
+        raise ValueError("native-size inference needs both sides >= %d (got %d x %d)" % (NATIVE_MIN_SIDE, h, w))
+    hp, wp = padded_size(h, w)
+    if hp * wp > NATIVE_TILED_MAX_PIXELS:
+        raise ValueError("tiled native-size inference: %d x %d pads to %d x %d = %d pixels, above the %d this package has been exercised at"
+                         % (h, w, hp, wp, hp * wp, NATIVE_TILED_MAX_PIXELS))
+    return hp, wp
+
+
+def native_tiles(hp, wp, core, halo):
+    """the tiles of an hp x wp image (multiples of 16) in row-major order: (cy0, cy1, cx0, cx1, ty0, ty1, tx0, tx1) -- the core, which the tile
+    accounts for, and the tile itself: the core extended by `halo` and clipped to the image, so that a tile edge at the image's border IS the
+    image's edge and the convolutions' own reflection there is the right one"""
+    out = []
+    for cy0 in range(0, hp, core):
+        cy1 = min(cy0 + core, hp)
+        for cx0 in range(0, wp, core):
+            cx1 = min(cx0 + core, wp)
+            out.append((cy0, cy1, cx0, cx1, max(cy0 - halo, 0), min(cy1 + halo, hp), max(cx0 - halo, 0), min(cx1 + halo, wp)))
+    return out
 
 
 def native_input(pixels):

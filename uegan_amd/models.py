@@ -202,8 +202,8 @@ class Interpolate(nn.Module):
         super().__init__()
         _require(scale_factor == 2 and mode == "bilinear" and align_corners, "Interpolate(2,'bilinear',True)")
 
-    def forward(self, x):
-        return ops.upsample2x(x)
+    def forward(self, x, at=None):
+        return ops.upsample2x(x, at=at)
 
 
 class _TouchParams(torch.autograd.Function):
@@ -244,9 +244,19 @@ class GAM(nn.Module):
         # column slice of the full [out_nc, 2*in_nc, 1, 1] parameter (no sliced copy, no scatter-add of the gradient)
         self._cfg = ops.ConvCfg(1, ops.PAD_REFLECT, ops.ACT_NONE, cin_used=in_nc)
 
-    def forward(self, x, x_lo=None):
+    def forward(self, x, x_lo=None, pre=None):
         """x_lo: x is a hi + lo pair (ops.set_precise; the full-resolution module ga1): weights as a pair, the conv's result and the normalised
-        output as pairs -> returns (y, y_lo)"""
+        output as pairs -> returns (y, y_lo).
+        pre: the [2, B, C] (mean, rstd) of W[:, :C] * x over the WHOLE image, of which x is a tile (Generator.tile_moments collected them): the conv runs
+        without its moments epilogue and the norm uses `pre`"""
+        if pre is not None:
+            z = self.fuse_in(x, x_lo)
+            if x_lo is not None:
+                y, y_lo = ops.instnorm_pair(z[0], z[1], pre)
+            else:
+                y = ops.instnorm(z, pre)
+            y = self._touch(y)
+            return y if x_lo is None else (y, y_lo)
         fuse = self.fuse[0]
         sn = ops.specnorm_sigma(fuse.weight_orig, fuse.weight_u, fuse.weight_v, do_iter=self.training) if self.use_sn else None
         # (the moments of the InstanceNorm ride along in the conv's epilogue where the streaming kernel takes the layer -- ga1, ga2 -- and the norm is
@@ -264,6 +274,17 @@ class GAM(nn.Module):
         y = self._touch(y)
         return y if x_lo is None else (y, y_lo)
 
+    def fuse_in(self, x, x_lo=None):
+        """z = W_fuse[:, :C] * x, the InstanceNorm's input, without its moments (x_lo: on a pair -> (z, z_lo)): what the two passes of tiled
+        inference share -- pass 1 accumulates the moments of z over each tile's window, pass 2 normalises z with the whole image's"""
+        fuse = self.fuse[0]
+        sn = ops.specnorm_sigma(fuse.weight_orig, fuse.weight_u, fuse.weight_v, do_iter=self.training) if self.use_sn else None
+        if x_lo is None:
+            return ops.conv2d(x, None, fuse.weight, None, self._cfg, sn=sn)
+        ex = ops.ConvExtras(x1_lo=x_lo, pair_w=True, want_lo=True)
+        z = ops.conv2d(x, None, fuse.weight, None, self._cfg, sn=sn, ex=ex)
+        return z, ex.y_lo
+
     def _touch(self, y):
         if torch.is_grad_enabled():
             dead = [p for p in (self.conv[0].weight, self.conv[2].weight, self.fuse[0].bias) if p.requires_grad]
@@ -278,6 +299,27 @@ class GAM(nn.Module):
             raise RuntimeError("GAM.hub: not with spectral norm")
         outs = ops.gam_hub(x, self.fuse[0].weight, self._cfg, x_act, n_x, wsb)
         return outs[:-1] + (self._touch(outs[-1]),)
+
+
+class Tile:
+    """Where a tile sits in the image it was cut from, for Generator.forward(x, tile=): origin (oy, ox) and the full padded size (GH, GW) in input
+    pixels, all multiples of 16, and the five whole-image moment tensors [2, B, C_k] of the attention modules ga1 .. ga5 (Generator.tile_moments ->
+    ops.moments_finish)."""
+    __slots__ = ("oy", "ox", "GH", "GW", "moments")
+
+    def __init__(self, oy, ox, GH, GW, moments):
+        self.oy, self.ox, self.GH, self.GW = int(oy), int(ox), int(GH), int(GW)
+        self.moments = tuple(moments)
+        if any(v % 16 for v in (self.oy, self.ox, self.GH, self.GW)) or self.oy < 0 or self.ox < 0 or len(self.moments) != 5:
+            raise ValueError("Tile: origin and size must be non-negative multiples of 16, with five moment tensors")
+
+    def check(self, x):
+        if self.oy + x.shape[2] > self.GH or self.ox + x.shape[3] > self.GW:
+            raise ValueError("Tile: a %d x %d tile at (%d, %d) does not lie inside the %d x %d image" % (x.shape[2], x.shape[3], self.oy, self.ox, self.GH, self.GW))
+
+    def at(self, k):
+        """the `at` of ops.upsample2x for the map at stride 2^k"""
+        return (self.oy >> k, self.ox >> k, self.GH >> k, self.GW >> k)
 
 
 class Generator(_InvalidatingModule):
@@ -326,9 +368,9 @@ class Generator(_InvalidatingModule):
         self.dec4.main[1].cfg.premasked = True          # consumer: mul (below)
 
     @staticmethod
-    def _up(block, x, ex=None):
-        # reference: conv1x1(bilinear_up(x)); here bilinear_up(conv1x1(x)) (exact, see module docstring)
-        return block[0](block[1](x, ex=ex))
+    def _up(block, x, ex=None, at=None):
+        # reference: conv1x1(bilinear_up(x)); here bilinear_up(conv1x1(x)) (exact, see module docstring).  at: x is a tile (Tile.at)
+        return block[0](block[1](x, ex=ex), at=at)
 
     @staticmethod
     def _check_input(x):
@@ -345,10 +387,19 @@ class Generator(_InvalidatingModule):
                                "call set_precise(False) for this network")
         return True
 
-    def forward(self, x):
+    def _check_tiled(self, what):
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("Generator.%s is inference only: call it in eval mode under torch.no_grad()" % what)
+
+    def forward(self, x, tile=None):
+        """tile: a `Tile` -- x is one tile of a larger image (tester.enhance_tiled): the attention modules normalise with the whole image's moments
+        and the up-samplings take the whole image's sampling phase.  Eval mode, no gradients."""
         _refuse_replica(self)
         self._check_input(x)
-        res, outs = self._body(ops.to_nhwc(x, pair=self._precise()), (x,))
+        if tile is not None:
+            self._check_tiled("forward(tile=)")
+            tile.check(x)
+        res, outs = self._body(ops.to_nhwc(x, pair=self._precise()), (x,), tile)
         return ops.residual_clamp(res, x, ops.ACT_TANH, given=outs)     # clamp(res + x, -1, 1), NCHW fp32 (outs: dec5.1's epilogue already wrote it)
 
     def forward_pair(self, xa, xb, xin=None):
@@ -370,28 +421,64 @@ class Generator(_InvalidatingModule):
         """the batch-concatenated NHWC copy of two image sets that forward_pair works on (for callers that queue the conversion early)"""
         return ops.to_nhwc_pair(xa, xb, pair=self._precise())
 
-    def _body_plain(self, xin):
+    def tile_moments_new(self, B, device):
+        """zeroed accumulators for tile_moments: five float64 [2, B, C_k], attention modules ga1 .. ga5 (C_k in the storage dtype's channel padding)"""
+        dt = ops.get_compute_dtype()
+        return [ops.moments_acc_new(B, ops.cpad(g.in_nc, dt), device) for g in (self.ga1, self.ga2, self.ga3, self.ga4, self.ga5)]
+
+    def tile_moments(self, x_tile, window, acc):
+        """Pass 1 of tiled inference.  x_tile: NCHW fp32 tile of a larger image; window = (y0, y1, x0, x1), multiples of 16 in the tile's own
+        coordinates: the part of the image this tile accounts for, at least data.NATIVE_TILE_HALO_ENC inside every tile edge that is not an image
+        edge.  Runs the encoder and the five attention modules' 1x1 convs and adds the moments of each result over the window (scaled to its level)
+        to acc (tile_moments_new).  Every attention module reads an encoder activation only, so no decoder layer runs.  Eval mode, no gradients."""
+        _refuse_replica(self)
+        self._check_input(x_tile)
+        self._check_tiled("tile_moments")
+        y0, y1, x0, x1 = (int(v) for v in window)
+        if any(v % 16 for v in (y0, y1, x0, x1)) or not (0 <= y0 < y1 <= x_tile.shape[2] and 0 <= x0 < x1 <= x_tile.shape[3]):
+            raise ValueError("tile_moments: window %s of a %d x %d tile: multiples of 16 inside the tile expected" % (((y0, y1, x0, x1),) + tuple(x_tile.shape[2:])))
+        P = self._precise()
+        X = ops.ConvExtras
+        ex1 = X(pair_w=True, dup_cin=True, want_lo=True) if P else None          # (the encoder exactly as _body runs it)
+        a1 = self.enc1(ops.to_nhwc(x_tile, pair=P), ex=ex1)
+        a2 = self.enc2(a1, ex=X(pair_w=True) if P else None)
+        a3 = self.enc3(a2)
+        a4 = self.enc4(a3)
+        a5 = self.enc5(a4)
+        for k, (ga, a) in enumerate(zip((self.ga1, self.ga2, self.ga3, self.ga4, self.ga5), (a1, a2, a3, a4, a5))):
+            win = tuple(v >> k for v in (y0, y1, x0, x1))
+            if P and k == 0:
+                z, z_lo = ga.fuse_in(a, ex1.y_lo)
+                ops.moments_window_acc(z, win, acc[k], x_lo=z_lo)
+            else:
+                ops.moments_window_acc(ga.fuse_in(a), win, acc[k])
+        return acc
+
+    def _body_plain(self, xin, tile=None):
         """models.py:46-71 layer by layer (non-default norm / activation / spectral-norm flags): no output aliases, no deferred
-        activation gradients -- autograd sums the gradients of the multi-consumer encoder activations"""
+        activation gradients -- autograd sums the gradients of the multi-consumer encoder activations.  tile: see forward (in eval mode the norms
+        of these flags use running statistics and spectral norm does not iterate: every layer but the attention modules is local)"""
+        pre, at = (tile.moments, tile.at) if tile is not None else ((None,) * 5, lambda k: None)
         x1 = self.enc1(xin)
         x2 = self.enc2(x1)
         x3 = self.enc3(x2)
         x4 = self.enc4(x3)
-        x5 = self.ga5(self.enc5(x4))
-        y1 = self.dec1(self._up(self.upsample1, x5), self.ga4(x4))
-        y2 = self.dec2(self._up(self.upsample2, y1), self.ga3(x3))
-        y3 = self.dec3(self._up(self.upsample3, y2), self.ga2(x2))
-        y4 = self.dec4(self._up(self.upsample4, y3), self.ga1(x1))
+        x5 = self.ga5(self.enc5(x4), pre=pre[4])
+        y1 = self.dec1(self._up(self.upsample1, x5, at=at(4)), self.ga4(x4, pre=pre[3]))
+        y2 = self.dec2(self._up(self.upsample2, y1, at=at(3)), self.ga3(x3, pre=pre[2]))
+        y3 = self.dec3(self._up(self.upsample3, y2, at=at(2)), self.ga2(x2, pre=pre[1]))
+        y4 = self.dec4(self._up(self.upsample4, y3, at=at(1)), self.ga1(x1, pre=pre[0]))
         return self.dec5[1](self.dec5[0](ops.mul(y4, x1)))
 
-    def _body(self, xin, xs):
+    def _body(self, xin, xs, tile=None):
         """models.py:46-71 on an NHWC (channel-padded) image batch -> (the tanh residual `res` (NHWC, channel-padded), outs).  xs: the NCHW fp32 image
         set(s) xin was made from; outs: clamp(res + x, -1, 1) per set when dec5.1's epilogue wrote it (16-bit storage), else None.
         ops.set_precise: the full-resolution chain image -> x1 -> ga1 -> y4 * x1 -> dec5.0 -> dec5.1 runs on hi + lo pairs (uegan_conv2d_fwd_ex)."""
         if not self.default_flags:
-            return self._body_plain(xin), None
+            return self._body_plain(xin, tile), None
         P = self._precise()
         X = ops.ConvExtras
+        pre, at = (tile.moments, tile.at) if tile is not None else ((None,) * 5, lambda k: None)      # tile: see forward
         # encoder activations with several consumers (next encoder stage, attention module, final modulation) come back as one
         # alias per consumer: their gradients meet inside the producing conv's activation-backward kernel (ops._ConvFn)
         ex1 = X(pair_w=True, dup_cin=True, want_lo=True) if P else None
@@ -417,20 +504,20 @@ class Generator(_InvalidatingModule):
         x3a, x3b = self.enc3(x2a, n_out=2)
         x4a, x4b = self.enc4(x3a, n_out=2)
         x5 = self.enc5(x4a)
-        x5 = self.ga5(x5)
+        x5 = self.ga5(x5, pre=pre[4])
 
-        y1 = self.dec1(self._up(self.upsample1, x5), self.ga4(x4b))
-        y2 = self.dec2(self._up(self.upsample2, y1), self.ga3(x3b))
-        y3 = self.dec3(self._up(self.upsample3, y2), g2 if wsb2 else self.ga2(x2b))
+        y1 = self.dec1(self._up(self.upsample1, x5, at=at(4)), self.ga4(x4b, pre=pre[3]))
+        y2 = self.dec2(self._up(self.upsample2, y1, at=at(3)), self.ga3(x3b, pre=pre[2]))
+        y3 = self.dec3(self._up(self.upsample3, y2, at=at(2)), g2 if wsb2 else self.ga2(x2b, pre=pre[1]))
         # y4.mul(x1) (models.py:69) is formed by dec4's epilogue from its fp32 result where a kernel does that (16-bit storage); `mul` then only records
         # the backward.  clamp(tanh(dec5.1) + x) likewise by dec5.1's epilogue (outs).
         if P:
-            g1, g1_lo = self.ga1(x1b, x_lo=x1_lo)
+            g1, g1_lo = self.ga1(x1b, x_lo=x1_lo, pre=pre[0])
             ex4 = X(x2_lo=g1_lo, pair_w=True, mul=x1c, mul_lo=x1_lo, want_mul_lo=True)
         else:
-            g1 = g1 if wsb1 else self.ga1(x1b)
+            g1 = g1 if wsb1 else self.ga1(x1b, pre=pre[0])
             ex4 = X(mul=x1c) if (xin.dtype != torch.float32 and ops.fuse_epilogues[0]) else None
-        y4 = self.dec4(self._up(self.upsample4, y3, ex=X(pair_w=True) if P else None), g1, ex=ex4)
+        y4 = self.dec4(self._up(self.upsample4, y3, ex=X(pair_w=True) if P else None, at=at(1)), g1, ex=ex4)
         prod = ops.mul(y4, x1c, act_a=ops.ACT_LRELU, given=ex4.prod if ex4 is not None else None)      # y4's LeakyReLU' applied in mul's backward
         ex5 = X(x1_lo=ex4.prod_lo, pair_w=True, want_lo=True) if P else None
         d50 = self.dec5[0](prod, ex=ex5)

@@ -844,8 +844,52 @@ def residual_clamp_pair(res, xa, xb, res_act=ACT_NONE, given=None):
     return _ResidualClampPair.apply(res, xa, xb, res_act, given)
 
 
-def upsample2x(x):
-    return _Upsample2x.apply(x)
+def upsample2x(x, at=None):
+    """at=(oy, ox, GH, GW): x is the tile at origin (oy, ox) of a global GH x GW map -> the matching window of the GLOBAL x2 result
+    (uegan_upsample2x_fwd_at: the align_corners sampling phase is the whole map's).  Forward only: raises while gradients are enabled."""
+    if at is None:
+        return _Upsample2x.apply(x)
+    if torch.is_grad_enabled():
+        raise RuntimeError("upsample2x(at=) is an inference kernel without a backward: call it under torch.no_grad()")
+    oy, ox, GH, GW = (int(v) for v in at)
+    x = x.contiguous()
+    B, H, W, Cc = x.shape
+    if not (0 <= oy and 0 <= ox and oy + H <= GH and ox + W <= GW):
+        raise ValueError("upsample2x: the %d x %d tile at (%d, %d) does not lie inside its %d x %d map" % (H, W, oy, ox, GH, GW))
+    y = torch.empty((B, 2 * H, 2 * W, Cc), dtype=x.dtype, device=x.device)
+    _chk(x)
+    L.check(lib().uegan_upsample2x_fwd_at(_dt(x), _p(x), _p(y), B, H, W, Cc, oy, ox, GH, GW, _stream()))
+    return y
+
+
+def moments_acc_new(B, Cc, device):
+    """zeroed accumulators for moments_window_acc: float64 [2, B, C] (sum z, sum z^2)"""
+    return torch.zeros((2, B, Cc), dtype=torch.float64, device=device)
+
+
+def moments_window_acc(x, window, acc, x_lo=None):
+    """acc (moments_acc_new) += (sum z, sum z^2) over rows [y0, y1) x columns [x0, x1) of the NHWC map x, read in place; x_lo: z is the pair
+    x + x_lo.  Deterministic: the same windows in the same order give the same bits (uegan_moments_window_acc)."""
+    y0, y1, x0, x1 = (int(v) for v in window)
+    B, H, W, Cc = x.shape
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError("moments_window_acc: rows [%d, %d) x columns [%d, %d) is no window of a %d x %d map" % (y0, y1, x0, x1, H, W))
+    if acc.dtype != torch.float64 or tuple(acc.shape) != (2, B, Cc) or (x_lo is not None and (x_lo.shape != x.shape or x_lo.dtype != x.dtype)):
+        raise ValueError("moments_window_acc: float64 [2, B, C] accumulators and a lo plane of x's shape expected")
+    _chk(x, x_lo, acc)
+    tmp = torch.empty((lib().uegan_moments_window_workspace_bytes(B, Cc) // 8,), dtype=torch.float64, device=x.device)
+    L.check(lib().uegan_moments_window_acc(_dt(x), _p(x), _p(x_lo), B, H, W, Cc, y0, y1, x0, x1, _p(acc[0]), _p(acc[1]), _p(tmp), _stream()))
+    return acc
+
+
+def moments_finish(acc, count, eps=IN_EPS):
+    """accumulators over `count` pixels per (image, channel) -> fp32 [2, B, C] (mean, rstd): the layout of StatsHolder.value and instnorm(pre=);
+    biased variance (uegan_moments_finish; eps < 0: the variance itself in place of rstd)"""
+    _chk(acc)
+    _, B, Cc = acc.shape
+    out = torch.empty((2, B, Cc), dtype=torch.float32, device=acc.device)
+    L.check(lib().uegan_moments_finish(_p(acc[0]), _p(acc[1]), float(count), float(eps), _p(out[0]), _p(out[1]), B * Cc, _stream()))
+    return out
 
 
 def maxpool2x2(x, in_act=ACT_NONE):

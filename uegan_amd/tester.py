@@ -3,7 +3,10 @@
     enhance(G, x)                     tester.py:58-67: `G.eval()`, `torch.no_grad()`, one `G(x)` per image
     GraphedGenerator(G, shape)        the same forward captured once into a hipGraph and replayed (batch-1 inference is
                                       ~60 dependent launches: launch latency, not arithmetic, sets its time)
-    enhance_native(G, pixels_u8)      an image at its OWN size: crop(G(reflect_extend(normalise(pixels)))), uint8 in, uint8 out
+    enhance_native(G, pixels_u8)      an image at its OWN size: crop(G(reflect_extend(normalise(pixels)))), uint8 in, uint8 out; tile=T: the same,
+                                      evaluated tile by tile for images above data.NATIVE_MAX_PIXELS
+    enhance_tiled(G, x, core)         G(x) for an fp32 image too large for one forward: two passes over tiles, exact
+    montage_place_u8(dst, images, ..) the quantised window of 1..4 images written into a larger uint8 image in place
     montage_u8(a, b, ...)             `to_uint8_image(torch.cat([a, b, ...], 3))` in one launch: the side-by-side sample / compare images
                                       (trainer.py:182-183,244-245, tester.py:73-74); window=(H, W): of the images' top-left H x W corner
     to_uint8_image(x)                 what tester.py:70-71 writes to a PNG: denorm (utils.py:128-130) + torchvision save_image's
@@ -123,7 +126,106 @@ def montage_u8(*images, window=None):
     return y
 
 
-def enhance_native(G, pixels_u8, compare=False):
+def montage_place_u8(dst, images, src_window, dst_origin, panel=None):
+    """Quantise the window (sy, sx, h, w) of 1..4 float32 [B,C,Hs,Ws] images straight into the uint8 [B,Hd,Wd,C] image `dst`: image k to rows
+    [dy, dy + h) and columns [dx + k*panel, dx + k*panel + w), (dy, dx) = dst_origin, panel = the montage's panel width (default w).  Bit for bit
+    `dst[:, dy:dy+h, dx+k*panel:dx+k*panel+w] = to_uint8_image(x_k[:, :, sy:sy+h, sx:sx+w])`; no other byte of dst is written
+    (uegan_montage_place_u8).  ValueError before any launch for a window or a destination that does not fit."""
+    n = len(images)
+    if not 1 <= n <= MONTAGE_MAX_IMAGES:
+        raise ValueError("montage_place_u8 takes 1..%d images (got %d)" % (MONTAGE_MAX_IMAGES, n))
+    for x in images:
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4:
+            raise TypeError("montage_place_u8 expects float32 [B,C,H,W] tensors")
+        if x.shape != images[0].shape or x.device != images[0].device:
+            raise ValueError("montage_place_u8: the images must have one shape and one device (got %s and %s)" % (tuple(images[0].shape), tuple(x.shape)))
+    B, C, Hs, Ws = images[0].shape
+    if not torch.is_tensor(dst) or dst.dtype != torch.uint8 or dst.dim() != 4 or dst.shape[0] != B or dst.shape[3] != C or not dst.is_contiguous():
+        raise TypeError("montage_place_u8 writes into a contiguous uint8 [B,Hd,Wd,C] image of the sources' batch and channels")
+    sy, sx, h, w = (int(v) for v in src_window)
+    dy, dx = (int(v) for v in dst_origin)
+    panel = w if panel is None else int(panel)
+    Hd, Wd = dst.shape[1:3]
+    if not (sy >= 0 and sx >= 0 and h >= 1 and w >= 1 and sy + h <= Hs and sx + w <= Ws):
+        raise ValueError("montage_place_u8: the %d x %d window at (%d, %d) does not fit the %d x %d images" % (h, w, sy, sx, Hs, Ws))
+    if not (dy >= 0 and dx >= 0 and panel >= w and dy + h <= Hd and dx + (n - 1) * panel + w <= Wd):
+        raise ValueError("montage_place_u8: %d panels of %d x %d (pitch %d) at (%d, %d) do not fit the %d x %d destination" % (n, h, w, panel, dy, dx, Hd, Wd))
+    xs = [x.detach().contiguous() for x in images]
+    ops._chk(dst, *xs)
+    L.check(ops.lib().uegan_montage_place_u8(ops._ptr_table(xs), n, dst.data_ptr(), B, C, Hs, Ws, sy, sx, h, w, Hd, Wd, dy, dx, panel, ops._stream()))
+    return dst
+
+
+def _tiled_moments(G, hp, wp, core, tile_of):
+    """pass 1 of the tiled forward: the attention modules' whole-image moments, from the encoder run over every tile (halo NATIVE_TILE_HALO_ENC);
+    tile_of(ty0, ty1, tx0, tx1) -> that tile of the padded image as fp32 NCHW"""
+    acc = None
+    for cy0, cy1, cx0, cx1, ty0, ty1, tx0, tx1 in data.native_tiles(hp, wp, core, data.NATIVE_TILE_HALO_ENC):
+        xt = tile_of(ty0, ty1, tx0, tx1)
+        if acc is None:
+            acc = G.tile_moments_new(xt.shape[0], xt.device)
+        G.tile_moments(xt, (cy0 - ty0, cy1 - ty0, cx0 - tx0, cx1 - tx0), acc)
+    return [ops.moments_finish(a, (hp >> k) * (wp >> k)) for k, a in enumerate(acc)]
+
+
+def _check_tiled(G, core, hp, wp):
+    """the refusals of the tiled forward, all before any launch -> (models.Tile, core)"""
+    from . import models
+    if G.training or torch.is_grad_enabled():
+        raise RuntimeError("the tiled forward is inference only: G.eval() and torch.no_grad()")
+    core = data.check_native_tile(core)
+    for tile in data.native_tiles(hp, wp, core, data.NATIVE_TILE_HALO):      # (the largest tiles: pass 1's have the smaller halo)
+        data.check_native_size(tile[5] - tile[4], tile[7] - tile[6])
+    return models.Tile, core
+
+
+def enhance_tiled(G, x, core):
+    """`enhance(G, x)` evaluated tile by tile: x fp32 [B,3,Hp,Wp] with sides that are multiples of 16 -> G(x), fp32, for an image too large for one
+    forward.  Not an approximation: pass 1 runs the encoder over tiles (halo 32) and accumulates the attention modules' moments over
+    the whole image (Generator.tile_moments); pass 2 runs the whole network per tile (halo 80, the generator's receptive-field radius 67 on the
+    stride-16 grid) with those moments and the image's own up-sampling phase (Generator.forward(tile=)) and keeps each tile's core.  `core`: the
+    tiles' core side, a multiple of 16, at least 32; tiles in row-major order.  G in eval mode, under torch.no_grad() (RuntimeError otherwise);
+    ValueError before any launch for a bad core or size."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != 3 or x.shape[2] % 16 or x.shape[3] % 16:
+        raise ValueError("enhance_tiled expects float32 [B,3,Hp,Wp] with Hp, Wp multiples of 16")
+    hp, wp = data.check_native_tiled_size(x.shape[2], x.shape[3])
+    Tile, core = _check_tiled(G, core, hp, wp)
+
+    def tile_of(ty0, ty1, tx0, tx1):
+        return x[:, :, ty0:ty1, tx0:tx1].contiguous()
+    moments = _tiled_moments(G, hp, wp, core, tile_of)
+    out = torch.empty_like(x)
+    for cy0, cy1, cx0, cx1, ty0, ty1, tx0, tx1 in data.native_tiles(hp, wp, core, data.NATIVE_TILE_HALO):
+        fake = G(tile_of(ty0, ty1, tx0, tx1), tile=Tile(ty0, tx0, hp, wp, moments))
+        out[:, :, cy0:cy1, cx0:cx1] = fake[:, :, cy0 - ty0:cy1 - ty0, cx0 - tx0:cx1 - tx0]
+    return out
+
+
+def _enhance_native_tiled(G, pixels_u8, compare, core):
+    if not torch.is_tensor(pixels_u8) or pixels_u8.dtype != torch.uint8 or pixels_u8.dim() != 4 or pixels_u8.shape[3] != 3 or not pixels_u8.is_contiguous():
+        raise ValueError("native_input expects a contiguous uint8 [B, h, w, 3] tensor")
+    B, h, w, _ = pixels_u8.shape
+    hp, wp = data.check_native_tiled_size(h, w)
+    G.eval()
+    Tile, core = _check_tiled(G, core, hp, wp)
+
+    def tile_of(ty0, ty1, tx0, tx1):
+        # (tile origins are multiples of 16: only the last row / column of tiles is ragged, and native_input's extension of those is the image's)
+        return data.native_input(pixels_u8[:, ty0:min(ty1, h), tx0:min(tx1, w)].contiguous())
+    moments = _tiled_moments(G, hp, wp, core, tile_of)
+    q = torch.empty((B, h, w, 3), dtype=torch.uint8, device=pixels_u8.device)
+    pair = torch.empty((B, h, 2 * w, 3), dtype=torch.uint8, device=pixels_u8.device) if compare else None
+    for cy0, cy1, cx0, cx1, ty0, ty1, tx0, tx1 in data.native_tiles(hp, wp, core, data.NATIVE_TILE_HALO):
+        xt = tile_of(ty0, ty1, tx0, tx1)
+        fake = G(xt, tile=Tile(ty0, tx0, hp, wp, moments))
+        win = (cy0 - ty0, cx0 - tx0, min(cy1, h) - cy0, min(cx1, w) - cx0)
+        montage_place_u8(q, [fake], win, (cy0, cx0))
+        if compare:
+            montage_place_u8(pair, [xt, fake], win, (cy0, cx0), panel=w)
+    return (q, pair) if compare else q
+
+
+def enhance_native(G, pixels_u8, compare=False, tile=None):
     """An image at its own size: uint8 [B,h,w,3] on the device (decoded RGB, both sides >= 32) -> the enhanced uint8 [B,h,w,3]; compare=True:
     also the raw | enhanced montage uint8 [B,h,2w,3] (tester.py:73-74).  The mode is DEFINED as
 
@@ -135,7 +237,15 @@ def enhance_native(G, pixels_u8, compare=False):
     hp - h), mode="reflect")))[:, :h, :w]` in every storage mode.  One consequence: the attention modules' global moments are taken over the
     extended image, so they include its up-to-15 reflected rows and columns (masked moments are not implemented).  The forward is eager
     (there is no hipGraph per padded shape).  ValueError before any launch: a side below 32, a padded area above data.NATIVE_MAX_PIXELS
-    per image, anything but a contiguous uint8 [B,h,w,3] tensor."""
+    per image, anything but a contiguous uint8 [B,h,w,3] tensor.
+
+    tile=T (a multiple of 16, at least 32): the same definition evaluated tile by tile, for images above that cap (up to
+    data.NATIVE_TILED_MAX_PIXELS): two passes over uint8 tiles of core T -- see enhance_tiled, of which this is bit for bit
+    `to_uint8_image(enhance_tiled(G, data.native_input(pixels), T), window=(h, w))` without ever holding the image in fp32: every tile is cut from
+    the bytes, and its core is quantised straight into the full-size result (montage_place_u8).  Nothing synchronises with the host between tiles."""
+    if tile is not None:
+        with torch.no_grad():
+            return _enhance_native_tiled(G, pixels_u8, compare, tile)
     x = data.native_input(pixels_u8)
     h, w = pixels_u8.shape[1:3]
     fake = enhance(G, x)
@@ -189,7 +299,7 @@ def mean_metric(values):
 
 
 def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suffix="testFakeExp", compare_dir=None,
-             compare_suffix="testRealRaw_testFakeExp"):
+             compare_suffix="testRealRaw_testFakeExp", native_tile=None):
     """Tester.test (tester.py:40-105) over a `uegan_amd.data` test loader: `G.eval()` forward per batch (:64-67), the enhanced image of
     every sample as `<name>_<tag>_<suffix>.png` in `save_dir` (:69-71: the 8-bit image torchvision's save_image writes; None: no
     files), and -- what calc_psnr / calc_ssim then compute from those files against the label images (:96-103) -- PSNR and SSIM of
@@ -199,7 +309,9 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suff
     Native mode (a `data.get_test_loader(root, 0)` loader, whose batches hold the decoded files as uint8 lists): every sample goes through
     `enhance_native` at its own size, the PNGs have the size of their source, the result gains "sizes" ([h, w] per image), and PSNR / SSIM
     compare against the label FILE's own pixels -- what calc_psnr / calc_ssim read; a label of another size than its raw image raises
-    ValueError naming both files (CalcPSNR.py:87 raises on it too).  The restriction below is that of the resizing mode only.
+    ValueError naming both files (CalcPSNR.py:87 raises on it too).  The restriction below is that of the resizing mode only.  A sample whose
+    padded area exceeds data.NATIVE_MAX_PIXELS is enhanced tile by tile (`enhance_native(tile=data.NATIVE_TILE)`); native_tile=T: every sample is,
+    with core T.
 
     Restriction: the label here is the loader's `img_exp` -- the label FILE resized to the test size by the loader's transform
     (data_loader.py:95-99) and re-quantised to 8 bits -- whereas calc_psnr / calc_ssim read the ORIGINAL files of test_label_dir.  The
@@ -222,7 +334,9 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suff
                                          % (batch.paths[i] + (lab.shape[1], lab.shape[2], raw.shape[1], raw.shape[2])))
             for i, name in enumerate(batch.img_name):
                 raw = batch.img_raw[i]
-                res = enhance_native(G, raw, compare=compare_dir is not None)
+                hp, wp = data.padded_size(raw.shape[1], raw.shape[2])
+                core = native_tile if native_tile is not None else (data.NATIVE_TILE if hp * wp > data.NATIVE_MAX_PIXELS else None)
+                res = enhance_native(G, raw, compare=compare_dir is not None, tile=core)
                 q, pair = res if compare_dir is not None else (res, None)
                 rec.add([name], q, pair, batch.img_exp[i] if metrics else None)
                 rec.sizes.append([int(raw.shape[1]), int(raw.shape[2])])
