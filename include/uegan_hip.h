@@ -376,6 +376,28 @@ int uegan_image_metrics_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, double*
                            int C, int crop_border, uegan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * PNG files written on the device (png.hip): what save_image does with the 8-bit images above, without the host.
+ * A file is: signature, IHDR (8-bit, colour type 2, no interlace), one IDAT chunk per BAND, IEND; every chunk CRC-32 is computed on the device.
+ * Every row is Paeth-filtered (3W + 1 bytes, the row above read from the pixels).  A band is the largest whole number of filtered rows that
+ * fits band_bytes (0: the default and maximum 65535; at least one row, so 3W + 1 <= band_bytes <= 65535).  The IDAT payloads are one zlib stream:
+ * header 78 01 in the first band's chunk, the big-endian Adler-32 of all filtered bytes at the end of the last one's.  Every band starts byte-aligned
+ * and is ONE dynamic-Huffman block of literals and the end-of-block symbol (257 literal/length code lengths <= 15, a complete canonical code; two
+ * distance codes of length 1; a fixed 4-bit code for the code-length alphabet), followed by an empty stored block (non-final bands) or carrying
+ * BFINAL (the last band) -- or one stored block when that is not smaller.  A band of n bytes therefore never takes more than n + 5.
+ * ------------------------------------------------------------------------------------------------- */
+/* Bytes one file can take at most (the per-image stride of `out` must be at least this), and the scratch the encoder needs for B images.
+ * W > 0: H x W RGB images.  W == 0: a raw buffer of H bytes cut into bands of band_bytes (uegan_deflate_bands; B = 1).  0 for bad arguments. */
+size_t uegan_png_capacity_bytes(int64_t H, int W, int band_bytes);
+size_t uegan_png_workspace_bytes(int B, int64_t H, int W, int band_bytes);
+/* images: DEVICE uint8 [B][H][W][3] -> B complete PNG files, file b at out + b * out_stride (out_stride >= uegan_png_capacity_bytes, DEVICE), its
+ * length in sizes[b] (DEVICE int64).  workspace: DEVICE, uegan_png_workspace_bytes, 16-byte aligned.  Five launches for the whole batch. */
+int uegan_png_encode(const uint8_t* images, int B, int H, int W, int band_bytes, uint8_t* out, int64_t out_stride, int64_t* sizes, void* workspace,
+                     uegan_stream_t stream);
+/* The same band coder on n arbitrary bytes (no filter, no PNG framing): out = a bare zlib stream of the bands (1 <= band_bytes <= 65535, 0: 65535),
+ * size[0] = its length.  out: uegan_png_capacity_bytes(n, 0, band_bytes) bytes; workspace: uegan_png_workspace_bytes(1, n, 0, band_bytes). */
+int uegan_deflate_bands(const uint8_t* data, int64_t n, int band_bytes, uint8_t* out, int64_t* size, void* workspace, uegan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Input pipeline on the device (data_loader.py:74-82 train transform, :95-100 test transform, :126 H2D)
  * ------------------------------------------------------------------------------------------------- */
 /* pixels: B (<= 64) crop windows of decoded 8-bit RGB images, DEVICE uint8 [B][in_h][in_w][3] (the RandomCrop of

@@ -161,7 +161,11 @@ SIGNATURES = {
     "uegan_montage_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_montage_crop_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_montage_place_u8": (c_int, [C.POINTER(c_vp), c_int, c_vp, c_int, c_int] + [c_int] * 11 + [c_vp]),
-    "uegan_native_input": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "uegan_png_capacity_bytes": (c_sz, [c_i64, c_int, c_int]),
+    "uegan_png_workspace_bytes": (c_sz, [c_int, c_i64, c_int, c_int]),
+    "uegan_png_encode": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "uegan_deflate_bands": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "uegan_native_input":(c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_nima_prepare": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),

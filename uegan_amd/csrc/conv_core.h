@@ -29,7 +29,14 @@ extern size_t g_prof_used;
 static inline int prof_key(int kind, bool bf16, int bn, int ks, int mode, int th, bool glds) {
   return (kind << 28) | ((bf16 ? 1 : 0) << 24) | (bn << 12) | (ks << 8) | (mode << 4) | ((th == 32 ? 2 : (th == 16 ? 1 : (th == 4 ? 3 : 0))) << 1) | (glds ? 1 : 0);
 }
+// the five launches of the PNG encoder (png.hip) share the records: bit 27 (free in the conv keys) + the launch's index
+static const int PROF_PNG = 1 << 27;
 static void prof_kernel_name(int key, char* buf, size_t n) {
+  if (key & PROF_PNG) {
+    static const char* const png[] = {"png_filter_hist_kernel", "png_code_kernel", "png_offsets_kernel", "png_pack_kernel", "png_layout_kernel"};
+    snprintf(buf, n, "%s", png[(key & 7) < 5 ? (key & 7) : 0]);
+    return;
+  }
   const int kind = (key >> 28) & 7, bn = (key >> 12) & 0xfff, ks = (key >> 8) & 15, mode = (key >> 4) & 15;
   const char* dt = ((key >> 24) & 1) ? "bf16" : "f32";
   if (kind == 0) snprintf(buf, n, "conv_gemm_kernel<%s,BN=%d,%s>", dt, bn, (key & 1) ? "glds" : "regstage");

@@ -1366,3 +1366,70 @@ class FusedAdamL2:
         if len(state) not in (0, len(self.params)) or len(steps) > 1:
             raise ValueError("FusedAdamL2 keeps ONE step counter: every parameter must carry the same `step` (got %s)" % sorted(steps))
         self.step_count = steps.pop() if steps else 0
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# PNG files on the device (csrc/png.hip)
+# --------------------------------------------------------------------------------------------------------------------
+PNG_MAX_BAND = 65535          # the default and largest band: what one stored deflate block holds
+
+
+def _png_band(band_bytes, least, what):
+    bb = PNG_MAX_BAND if band_bytes is None else int(band_bytes)
+    if not least <= bb <= PNG_MAX_BAND:
+        raise ValueError("%s: band_bytes %d is not in [%d, %d]" % (what, bb, least, PNG_MAX_BAND))
+    return bb
+
+
+def _png_fetch(out, stride, sizes):
+    """one read of the sizes, one D2H copy of the used bytes -> list[bytes]"""
+    sizes = [int(v) for v in sizes.tolist()]
+    used = out[:sizes[0]] if len(sizes) == 1 else torch.cat([out[i * stride:i * stride + n] for i, n in enumerate(sizes)])
+    host = used.cpu().numpy().tobytes()
+    ends = [0]
+    for n in sizes:
+        ends.append(ends[-1] + n)
+    return [host[ends[i]:ends[i + 1]] for i in range(len(sizes))]
+
+
+def png_encode(images_u8, band_bytes=None):
+    """uint8 [B,H,W,3] on the device -> B complete 8-bit RGB PNG files as bytes, every per-byte step on the device (uegan_png_encode): Paeth filter,
+    one dynamic-Huffman deflate block per band of whole rows (at most band_bytes filtered bytes, default 65535), chunk CRCs, Adler-32.  The host
+    reads the B sizes and copies the used bytes.  Refused before any launch: anything but a contiguous uint8 [B,H,W,3] tensor (TypeError), an
+    empty image, a row that does not fit a band (3W + 1 > 65535), band_bytes outside [3W + 1, 65535] (ValueError)."""
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3 or not images_u8.is_contiguous():
+        raise TypeError("png_encode expects a contiguous uint8 [B,H,W,3] tensor")
+    B, H, W, _ = images_u8.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError("png_encode: empty image stack %s" % (tuple(images_u8.shape),))
+    row = 3 * W + 1
+    if row > PNG_MAX_BAND:
+        raise ValueError("png_encode: a filtered row of %d pixels (%d bytes) does not fit a band of %d bytes" % (W, row, PNG_MAX_BAND))
+    bb = _png_band(band_bytes, row, "png_encode")
+    _chk(images_u8)
+    dev = images_u8.device
+    stride = (lib().uegan_png_capacity_bytes(H, W, bb) + 15) // 16 * 16
+    out = torch.empty((B * stride,), dtype=torch.uint8, device=dev)
+    sizes = torch.empty((B,), dtype=torch.int64, device=dev)
+    ws = torch.empty((lib().uegan_png_workspace_bytes(B, H, W, bb),), dtype=torch.uint8, device=dev)
+    L.check(lib().uegan_png_encode(images_u8.data_ptr(), B, H, W, bb, out.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
+    return _png_fetch(out, stride, sizes)
+
+
+def deflate_bands(data_u8, band_bytes=None):
+    """the band coder of png_encode on a 1-D uint8 tensor, without filter and PNG framing: a bare zlib stream of one dynamic-Huffman (or stored) block
+    per band_bytes bytes (uegan_deflate_bands) -> bytes; band_bytes in [1, 65535]"""
+    if not torch.is_tensor(data_u8) or data_u8.dtype != torch.uint8 or data_u8.dim() != 1 or not data_u8.is_contiguous():
+        raise TypeError("deflate_bands expects a contiguous 1-D uint8 tensor")
+    n = data_u8.numel()
+    if n < 1:
+        raise ValueError("deflate_bands: no data")
+    bb = _png_band(band_bytes, 1, "deflate_bands")
+    _chk(data_u8)
+    dev = data_u8.device
+    cap = lib().uegan_png_capacity_bytes(n, 0, bb)
+    out = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    size = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = torch.empty((lib().uegan_png_workspace_bytes(1, n, 0, bb),), dtype=torch.uint8, device=dev)
+    L.check(lib().uegan_deflate_bands(data_u8.data_ptr(), n, bb, out.data_ptr(), size.data_ptr(), ws.data_ptr(), _stream()))
+    return _png_fetch(out, cap, size)[0]

@@ -16,6 +16,7 @@ What differs from the reference, on purpose:
   * --test_img_size 0 is the native size (tester.enhance_native): no resize, outputs at the size of their source, "sizes" in test_metrics.json.
   * the training loader draws from its own generator seeded with --seed (`loader_generator`), not from the global one: what validation or a
     sample draws never shifts the training data.
+  * UEGAN_PNG_ENCODER=device in the environment: samples, validation and test images are encoded on the device (tester.write_pngs); same pixels.
   * a step that prints nothing reads nothing from the device: the five losses are fetched (Trainer.loss_items) every --info_step only.
 """
 import json
@@ -113,11 +114,6 @@ def _load_nima(args, dev):
     model = nima.NIMA()
     model.load_state_dict(torch.load(args.nima_weights, map_location="cpu", weights_only=True))
     return model.to(dev).eval()
-
-
-def _write_png(path, hwc_u8):
-    from PIL import Image
-    Image.fromarray(hwc_u8, "RGB").save(path)
 
 
 class _Best:
@@ -232,9 +228,8 @@ def _train_loop(args, dev, paths, G, D, percep, scorer, loader, val_loader):
                                               v["g_adv"], v["g_idt"]))
             _append(log_file, dict(step=step + 1, epoch=epoch, elapsed_s=round(elapsed, 3), **v))
         if (step + 1) % args.sample_step == 0:                                                                         # :180-183
-            host = tester.montage_u8(real_raw, T.fake_exp, real_exp).cpu().numpy()
-            for i, name in enumerate(batch.img_name):
-                _write_png(os.path.join(paths["sample_path"], "{:s}_{:0>3.2f}_{:0>2d}_realRaw_fakeExp_realExp.png".format(name, epoch, i)), host[i])
+            tester.write_pngs([os.path.join(paths["sample_path"], "{:s}_{:0>3.2f}_{:0>2d}_realRaw_fakeExp_realExp.png".format(name, epoch, i))
+                               for i, name in enumerate(batch.img_name)], tester.montage_u8(real_raw, T.fake_exp, real_exp))
         if model_save_step and (step + 1) % model_save_step == 0:                                                      # :186-210
             T.save_checkpoint(os.path.join(paths["model_save_path"], checkpoint_name(args, epoch)), epoch)
             print("======= Save model checkpoints into {} ======".format(paths["model_save_path"]))
@@ -289,7 +284,22 @@ def test(args):
     return res
 
 
+PNG_ENCODER_ENV = "UEGAN_PNG_ENCODER"
+
+
+def _apply_png_encoder():
+    """UEGAN_PNG_ENCODER=device|pillow in the environment selects who encodes every PNG of the run (tester.set_png_encoder); unset: the selection
+    stays (default "pillow").  It is not a flag: the flag set is the reference's."""
+    name = os.environ.get(PNG_ENCODER_ENV)
+    if name is None:
+        return
+    if name not in tester.PNG_ENCODERS:
+        raise ValueError("%s=%r: expected one of %s" % (PNG_ENCODER_ENV, name, ", ".join(tester.PNG_ENCODERS)))
+    tester.set_png_encoder(name)
+
+
 def main(argv=None):
+    _apply_png_encoder()
     args = argv if hasattr(argv, "mode") else config.get_config(argv)
     if args.mode not in ("train", "test"):
         raise NotImplementedError("Mode [{}] is not found".format(args.mode))                                          # main.py:50

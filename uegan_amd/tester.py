@@ -14,6 +14,8 @@
     calculate_psnr / calculate_ssim   metrics/CalcPSNR.py:85-92 and metrics/CalcSSIM.py:63 (skimage defaults) with the 4-pixel
                                       border crop both scripts apply (:24,56), computed by libuegan_hip.so kernels
     mean_metric(values)               the TRUE mean; the reference's directory averages divide by N-1 (CalcPSNR.py:77, CalcSSIM.py:75)
+    write_pngs(paths, images_u8)      the 8-bit images as PNG files, by the encoder set_png_encoder selects: "pillow" (the default: Image.save on the
+                                      host) or "device" (ops.png_encode: filter, deflate and CRCs in libuegan_hip.so, the host only writes)
     run_test(G, loader, ...)          the loop of Tester.test (tester.py:40-105): enhance every batch of a test loader, write the
                                       PNGs `save_image` would write, PSNR / SSIM against the labels on the device, and the NIMA
                                       score of the enhanced images (uegan_amd/nima.py) when a scorer is passed
@@ -255,6 +257,40 @@ def enhance_native(G, pixels_u8, compare=False, tile=None):
     return q, montage_u8(x, fake, window=(h, w))
 
 
+PNG_ENCODERS = ("pillow", "device")
+_png_encoder = "pillow"
+
+
+def set_png_encoder(name):
+    """who encodes the PNG files write_pngs writes: "pillow" (the default; files as before) or "device" (ops.png_encode: same pixels, another
+    deflate stream).  Anything else: ValueError."""
+    global _png_encoder
+    if name not in PNG_ENCODERS:
+        raise ValueError("unknown PNG encoder %r (one of %s)" % (name, ", ".join(PNG_ENCODERS)))
+    _png_encoder = name
+
+
+def get_png_encoder():
+    return _png_encoder
+
+
+def write_pngs(paths, images_u8):
+    """images_u8: uint8 [B,H,W,3] on the device; image i goes to paths[i] as an 8-bit RGB PNG (what save_image writes), encoded by the selected
+    encoder.  Both encoders' files decode to the same pixels."""
+    paths = list(paths)
+    if len(paths) != images_u8.shape[0]:
+        raise ValueError("write_pngs: %d paths for %d images" % (len(paths), images_u8.shape[0]))
+    if _png_encoder == "device":
+        for path, blob in zip(paths, ops.png_encode(images_u8.contiguous())):
+            with open(path, "wb") as f:
+                f.write(blob)
+        return
+    from PIL import Image
+    host = images_u8.cpu().numpy()
+    for i, path in enumerate(paths):
+        Image.fromarray(host[i], "RGB").save(path)
+
+
 def _as_stack(img):
     if img.dtype != torch.uint8:
         raise TypeError("metrics take uint8 HWC / BHWC images (to_uint8_image)")
@@ -374,10 +410,7 @@ class _TestRecord:
         self.names += names
         for (d, suffix), images in zip(self.dirs, (q, pair)):
             if d is not None and images is not None:
-                from PIL import Image
-                host = images.cpu().numpy()
-                for i, name in enumerate(names):
-                    Image.fromarray(host[i], "RGB").save(os.path.join(d, "%s_%s_%s.png" % (name, self.tag, suffix)))
+                write_pngs([os.path.join(d, "%s_%s_%s.png" % (name, self.tag, suffix)) for name in names], images)
 
     def result(self):
         out = {"names": self.names, "psnr": self.psnr, "ssim": self.ssim}
