@@ -398,6 +398,32 @@ int uegan_png_encode(const uint8_t* images, int B, int H, int W, int band_bytes,
 int uegan_deflate_bands(const uint8_t* data, int64_t n, int band_bytes, uint8_t* out, int64_t* size, void* workspace, uegan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Baseline JPEG files written on the device (jpeg.hip).  One layout: SOI, APP0 (JFIF 1.01, density 1:1, no thumbnail), two DQT (8-bit; 0 luma,
+ * 1 chroma: Annex K.1 / K.2 scaled by libjpeg's quality rule), SOF0 (8-bit, Y Cb Cr; subsampling 0: 1x1 1x1 1x1 = 4:4:4, 2: 2x2 1x1 1x1 = 4:2:0,
+ * the codes Pillow uses), four DHT (the Annex K.3 tables: DC luma, AC luma, DC chroma, AC chroma), DRI, one interleaved SOS, entropy data, EOI.
+ * The restart interval is one MCU row (DRI = ceil(W / mcu_w), mcu 8 or 16): interval k is followed by RST(k mod 8), the last one by EOI; every
+ * interval starts byte-aligned with the DC predictors at 0.  H and W are at most 65535 (the SOF0 fields), so DRI always fits its 16 bits.
+ * JFIF full-range RGB -> YCbCr, edges replicated to the MCU grid, 4:2:0 chroma = fp32 mean of 2x2, fp32 DCT, round-half-away(coef / q).
+ * ------------------------------------------------------------------------------------------------- */
+/* HOST ONLY: the 128 table entries for quality 1..100, zigzag order, luma then chroma.  UEGAN_E_INVALID for another quality. */
+int uegan_jpeg_qtables(int quality, uint8_t* out128);
+/* Bytes one file can take at most: every block at the longest codes of the standard tables (11 + 11 bits DC, 63 x (16 + 10) bits AC), every byte
+ * stuffed, per interval a padding byte and a marker, + the 629 header bytes.  Scratch for B images.  0 for bad arguments. */
+size_t uegan_jpeg_capacity_bytes(int H, int W, int subsampling);
+size_t uegan_jpeg_workspace_bytes(int B, int H, int W, int subsampling);
+/* images: DEVICE uint8 [B][H][W][3] -> B complete files, file b at out + b * out_stride, its length in sizes[b] (DEVICE int64).  workspace: DEVICE,
+ * uegan_jpeg_workspace_bytes, 16-byte aligned.  The capacity above is far more than a photograph takes, so the call may be split in two:
+ *   out == NULL              the sizing step: coefficients, code lengths and offsets stay in the workspace, sizes[b] = the exact file sizes;
+ *   images == NULL           the writing step of a preceding sizing step with the same arguments, workspace and sizes;
+ *   both given               both steps.
+ * out_stride may be below the capacity: an image whose file does not fit is not written (sizes[b] > out_stride tells). */
+int uegan_jpeg_encode(const uint8_t* images, int B, int H, int W, int quality, int subsampling, uint8_t* out, int64_t out_stride, int64_t* sizes,
+                      void* workspace, uegan_stream_t stream);
+/* Stage 1 alone: the quantised coefficients, DEVICE int16 [B][component][block row][block col][64] in zigzag order (4:2:0: the Y plane has
+ * 2 x 2 blocks per MCU, so the three planes of an image differ in size; every plane covers whole MCUs). */
+int uegan_jpeg_coeffs(const uint8_t* images, int B, int H, int W, int quality, int subsampling, int16_t* coeffs, uegan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Input pipeline on the device (data_loader.py:74-82 train transform, :95-100 test transform, :126 H2D)
  * ------------------------------------------------------------------------------------------------- */
 /* pixels: B (<= 64) crop windows of decoded 8-bit RGB images, DEVICE uint8 [B][in_h][in_w][3] (the RandomCrop of

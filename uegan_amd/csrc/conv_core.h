@@ -31,10 +31,16 @@ static inline int prof_key(int kind, bool bf16, int bn, int ks, int mode, int th
 }
 // the five launches of the PNG encoder (png.hip) share the records: bit 27 (free in the conv keys) + the launch's index
 static const int PROF_PNG = 1 << 27;
+static const int PROF_JPEG = 1 << 26;      // ... and the launches of the JPEG encoder (jpeg.hip): bit 26, free as well
 static void prof_kernel_name(int key, char* buf, size_t n) {
   if (key & PROF_PNG) {
     static const char* const png[] = {"png_filter_hist_kernel", "png_code_kernel", "png_offsets_kernel", "png_pack_kernel", "png_layout_kernel"};
     snprintf(buf, n, "%s", png[(key & 7) < 5 ? (key & 7) : 0]);
+    return;
+  }
+  if (key & PROF_JPEG) {
+    static const char* const jpeg[] = {"jpeg_tables_kernel", "jpeg_coeffs_kernel", "jpeg_pack_kernel<size>", "jpeg_offsets_kernel", "jpeg_pack_kernel<write>"};
+    snprintf(buf, n, "%s", jpeg[(key & 7) < 5 ? (key & 7) : 0]);
     return;
   }
   const int kind = (key >> 28) & 7, bn = (key >> 12) & 0xfff, ks = (key >> 8) & 15, mode = (key >> 4) & 15;

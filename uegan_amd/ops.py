@@ -1382,8 +1382,8 @@ def _png_band(band_bytes, least, what):
 
 
 def _png_fetch(out, stride, sizes):
-    """one read of the sizes, one D2H copy of the used bytes -> list[bytes]"""
-    sizes = [int(v) for v in sizes.tolist()]
+    """one read of the sizes (a device tensor, or the list already read), one D2H copy of the used bytes -> list[bytes]"""
+    sizes = [int(v) for v in (sizes.tolist() if torch.is_tensor(sizes) else sizes)]
     used = out[:sizes[0]] if len(sizes) == 1 else torch.cat([out[i * stride:i * stride + n] for i, n in enumerate(sizes)])
     host = used.cpu().numpy().tobytes()
     ends = [0]
@@ -1433,3 +1433,104 @@ def deflate_bands(data_u8, band_bytes=None):
     ws = torch.empty((lib().uegan_png_workspace_bytes(1, n, 0, bb),), dtype=torch.uint8, device=dev)
     L.check(lib().uegan_deflate_bands(data_u8.data_ptr(), n, bb, out.data_ptr(), size.data_ptr(), ws.data_ptr(), _stream()))
     return _png_fetch(out, cap, size)[0]
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Baseline JPEG files on the device (csrc/jpeg.hip)
+# --------------------------------------------------------------------------------------------------------------------
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:0": 2}          # name -> the code of the C ABI (Pillow's)
+JPEG_MAX_SIDE = 65535                                 # the SOF0 fields; it also keeps the restart interval of one MCU row inside DRI's 16 bits
+
+
+def _jpeg_args(images_u8, quality, subsampling, what):
+    """the refusals shared by the three entry points, all before any launch -> (B, H, W, quality, subsampling code)"""
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3 or not images_u8.is_contiguous():
+        raise TypeError("%s expects a contiguous uint8 [B,H,W,3] tensor" % what)
+    B, H, W, _ = images_u8.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError("%s: empty image stack %s" % (what, tuple(images_u8.shape)))
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("%s: quality %r is not an integer in [1, 100]" % (what, quality))
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("%s: subsampling %r is not one of %s" % (what, subsampling, ", ".join(JPEG_SUBSAMPLINGS)))
+    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+        raise ValueError("%s: %d x %d exceeds %d (SOF0's 16-bit fields, and DRI's for a restart interval of one MCU row)" % (what, H, W, JPEG_MAX_SIDE))
+    return B, H, W, quality, JPEG_SUBSAMPLINGS[subsampling]
+
+
+def jpeg_qtables(quality):
+    """the 128 quantisation table entries of `quality` (Annex K.1 / K.2 by libjpeg's rule), zigzag order, luma then chroma (host only)"""
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("jpeg_qtables: quality %r is not an integer in [1, 100]" % (quality,))
+    buf = (C.c_uint8 * 128)()
+    L.check(lib().uegan_jpeg_qtables(quality, buf))
+    return list(buf)
+
+
+def jpeg_capacity(H, W, subsampling="4:4:4"):
+    """bytes no file of this shape can exceed (uegan_jpeg_capacity_bytes: every code at its longest, every byte stuffed)"""
+    return int(lib().uegan_jpeg_capacity_bytes(H, W, JPEG_SUBSAMPLINGS[subsampling]))
+
+
+def jpeg_coeffs(images_u8, quality=95, subsampling="4:4:4"):
+    """stage 1 of jpeg_encode alone (uegan_jpeg_coeffs): the quantised DCT coefficients as [Y, Cb, Cr], each an int16 device tensor
+    [B, block rows, block cols, 64] in zigzag order (4:2:0: Y has twice the rows and columns of Cb / Cr)"""
+    B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_coeffs")
+    _chk(images_u8)
+    mcu = 16 if ss else 8
+    my, mx = -(-H // mcu), -(-W // mcu)
+    shapes = [(2 * my, 2 * mx) if ss else (my, mx), (my, mx), (my, mx)]
+    per = sum(r * c for r, c in shapes)
+    flat = torch.empty((B, per, 64), dtype=torch.int16, device=images_u8.device)
+    L.check(lib().uegan_jpeg_coeffs(images_u8.data_ptr(), B, H, W, q, ss, flat.data_ptr(), _stream()))
+    planes, at = [], 0
+    for r, c in shapes:
+        planes.append(flat[:, at:at + r * c].reshape(B, r, c, 64))
+        at += r * c
+    return planes
+
+
+def _jpeg_sizing(images_u8, B, H, W, q, ss):
+    """the sizing step -> (sizes tensor, workspace): coefficients, code lengths and offsets stay in the workspace"""
+    dev = images_u8.device
+    sizes = torch.empty((B,), dtype=torch.int64, device=dev)
+    ws = torch.empty((lib().uegan_jpeg_workspace_bytes(B, H, W, ss),), dtype=torch.uint8, device=dev)
+    L.check(lib().uegan_jpeg_encode(images_u8.data_ptr(), B, H, W, q, ss, None, 0, sizes.data_ptr(), ws.data_ptr(), _stream()))
+    return sizes, ws
+
+
+def jpeg_sizes(images_u8, quality=95, subsampling="4:4:4"):
+    """the exact sizes of the files jpeg_encode would return, without writing them (the sizing step of uegan_jpeg_encode) -> list of B ints"""
+    B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_sizes")
+    _chk(images_u8)
+    return [int(v) for v in _jpeg_sizing(images_u8, B, H, W, q, ss)[0].tolist()]
+
+
+def jpeg_encode(images_u8, quality=95, subsampling="4:4:4", out=None):
+    """uint8 [B,H,W,3] on the device -> B complete baseline JPEG files as bytes (uegan_jpeg_encode: JFIF YCbCr, fp32 DCT, the Annex K tables, one
+    restart interval per MCU row), every per-pixel and per-bit step on the device.  The capacity bound of a shape is far above what a photograph
+    takes, so the call is split: the sizing step leaves the exact file sizes on the device, the host reads them, allocates exactly that and runs
+    the writing step; then one D2H copy of the files.  out: a uint8 device tensor [B, stride] with stride >= jpeg_capacity(H, W, subsampling) to
+    encode into in ONE call instead (the files are returned all the same; bytes of `out` behind a file are left as they were).
+    Refused before any launch: anything but a contiguous uint8 [B,H,W,3] tensor (TypeError); an empty batch, a quality outside 1..100, a subsampling
+    other than "4:4:4" / "4:2:0", a side above 65535 (ValueError)."""
+    B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_encode")
+    dev = images_u8.device
+    if out is not None:
+        cap = lib().uegan_jpeg_capacity_bytes(H, W, ss)
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < cap or not out.is_contiguous() \
+                or out.device != dev:
+            raise TypeError("jpeg_encode: out must be a contiguous uint8 [%d, >= %d] tensor on the images' device" % (B, cap))
+        _chk(images_u8, out)
+        stride = out.shape[1]
+        sizes = torch.empty((B,), dtype=torch.int64, device=dev)
+        ws = torch.empty((lib().uegan_jpeg_workspace_bytes(B, H, W, ss),), dtype=torch.uint8, device=dev)
+        L.check(lib().uegan_jpeg_encode(images_u8.data_ptr(), B, H, W, q, ss, out.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
+        return _png_fetch(out.view(-1), stride, sizes)
+    _chk(images_u8)
+    sizes, ws = _jpeg_sizing(images_u8, B, H, W, q, ss)
+    known = [int(v) for v in sizes.tolist()]
+    stride = (max(known) + 15) // 16 * 16
+    buf = torch.empty((B * stride,), dtype=torch.uint8, device=dev)
+    L.check(lib().uegan_jpeg_encode(None, B, H, W, q, ss, buf.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
+    return _png_fetch(buf, stride, known)

@@ -17,6 +17,8 @@ What differs from the reference, on purpose:
   * the training loader draws from its own generator seeded with --seed (`loader_generator`), not from the global one: what validation or a
     sample draws never shifts the training data.
   * UEGAN_PNG_ENCODER=device in the environment: samples, validation and test images are encoded on the device (tester.write_pngs); same pixels.
+  * UEGAN_IMAGE_FORMAT=jpeg (with UEGAN_JPEG_QUALITY=1..100, default 95) in the environment: those files are baseline JPEGs named .jpg, encoded on
+    the device (tester.write_images); the metrics are computed before encoding and equal those of a PNG run.
   * a step that prints nothing reads nothing from the device: the five losses are fetched (Trainer.loss_items) every --info_step only.
 """
 import json
@@ -228,8 +230,8 @@ def _train_loop(args, dev, paths, G, D, percep, scorer, loader, val_loader):
                                               v["g_adv"], v["g_idt"]))
             _append(log_file, dict(step=step + 1, epoch=epoch, elapsed_s=round(elapsed, 3), **v))
         if (step + 1) % args.sample_step == 0:                                                                         # :180-183
-            tester.write_pngs([os.path.join(paths["sample_path"], "{:s}_{:0>3.2f}_{:0>2d}_realRaw_fakeExp_realExp.png".format(name, epoch, i))
-                               for i, name in enumerate(batch.img_name)], tester.montage_u8(real_raw, T.fake_exp, real_exp))
+            tester.write_images([os.path.join(paths["sample_path"], "{:s}_{:0>3.2f}_{:0>2d}_realRaw_fakeExp_realExp.png".format(name, epoch, i))
+                                 for i, name in enumerate(batch.img_name)], tester.montage_u8(real_raw, T.fake_exp, real_exp))
         if model_save_step and (step + 1) % model_save_step == 0:                                                      # :186-210
             T.save_checkpoint(os.path.join(paths["model_save_path"], checkpoint_name(args, epoch)), epoch)
             print("======= Save model checkpoints into {} ======".format(paths["model_save_path"]))
@@ -298,8 +300,31 @@ def _apply_png_encoder():
     tester.set_png_encoder(name)
 
 
+IMAGE_FORMAT_ENV = "UEGAN_IMAGE_FORMAT"
+JPEG_QUALITY_ENV = "UEGAN_JPEG_QUALITY"
+
+
+def _apply_image_format():
+    """UEGAN_IMAGE_FORMAT=png|jpeg in the environment selects the container of every image the run writes (tester.set_image_format), and
+    UEGAN_JPEG_QUALITY=1..100 the quality of "jpeg" (default 95); unset: the selection stays (default "png").  Any other value is refused by name,
+    and so is a quality without UEGAN_IMAGE_FORMAT=jpeg.  They are not flags: the flag set is the reference's."""
+    name, quality = os.environ.get(IMAGE_FORMAT_ENV), os.environ.get(JPEG_QUALITY_ENV)
+    if name is not None and name not in tester.IMAGE_FORMATS:
+        raise ValueError("%s=%r: expected one of %s" % (IMAGE_FORMAT_ENV, name, ", ".join(tester.IMAGE_FORMATS)))
+    if quality is not None:
+        if name != "jpeg":
+            raise ValueError("%s=%r needs %s=jpeg" % (JPEG_QUALITY_ENV, quality, IMAGE_FORMAT_ENV))
+        if not (quality.isascii() and quality.isdigit() and 1 <= int(quality) <= 100):
+            raise ValueError("%s=%r: expected an integer in [1, 100]" % (JPEG_QUALITY_ENV, quality))
+    if name == "jpeg":
+        tester.set_image_format("jpeg", quality=int(quality) if quality is not None else 95)
+    elif name == "png":
+        tester.set_image_format("png")
+
+
 def main(argv=None):
     _apply_png_encoder()
+    _apply_image_format()
     args = argv if hasattr(argv, "mode") else config.get_config(argv)
     if args.mode not in ("train", "test"):
         raise NotImplementedError("Mode [{}] is not found".format(args.mode))                                          # main.py:50

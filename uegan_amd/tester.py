@@ -16,6 +16,8 @@
     mean_metric(values)               the TRUE mean; the reference's directory averages divide by N-1 (CalcPSNR.py:77, CalcSSIM.py:75)
     write_pngs(paths, images_u8)      the 8-bit images as PNG files, by the encoder set_png_encoder selects: "pillow" (the default: Image.save on the
                                       host) or "device" (ops.png_encode: filter, deflate and CRCs in libuegan_hip.so, the host only writes)
+    write_images(paths, images_u8)    ... by the format set_image_format selects: "png" (write_pngs, the default) or "jpeg" (ops.jpeg_encode: baseline
+                                      JPEG on the device, files named .jpg); returns the paths written
     run_test(G, loader, ...)          the loop of Tester.test (tester.py:40-105): enhance every batch of a test loader, write the
                                       PNGs `save_image` would write, PSNR / SSIM against the labels on the device, and the NIMA
                                       score of the enhanced images (uegan_amd/nima.py) when a scorer is passed
@@ -291,6 +293,52 @@ def write_pngs(paths, images_u8):
         Image.fromarray(host[i], "RGB").save(path)
 
 
+IMAGE_FORMATS = ("png", "jpeg")
+_image_format = ("png", 95, "4:4:4")
+
+
+def set_image_format(name, quality=95, subsampling="4:4:4"):
+    """the container write_images writes: "png" (the default: write_pngs, every file name and byte as before) or "jpeg" (ops.jpeg_encode with this
+    quality, 1..100, and subsampling, "4:4:4" or "4:2:0": baseline JPEG files named .jpg, always encoded on the device -- there is no Pillow arm,
+    and the PNG encoder selection does not matter to it).  Anything else: ValueError, and the selection stays."""
+    global _image_format
+    if name not in IMAGE_FORMATS:
+        raise ValueError("unknown image format %r (one of %s)" % (name, ", ".join(IMAGE_FORMATS)))
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("JPEG quality %r is not an integer in [1, 100]" % (quality,))
+    if subsampling not in ops.JPEG_SUBSAMPLINGS:
+        raise ValueError("JPEG subsampling %r is not one of %s" % (subsampling, ", ".join(ops.JPEG_SUBSAMPLINGS)))
+    _image_format = (name, quality, subsampling)
+
+
+def get_image_format():
+    """(name, quality, subsampling) as set_image_format took them; quality and subsampling only matter to the "jpeg" format"""
+    return _image_format
+
+
+def image_path(path):
+    """the name write_images gives the file asked for as `path`: the same for "png"; for "jpeg" a .png suffix becomes .jpg"""
+    if _image_format[0] == "jpeg" and path.endswith(".png"):
+        return path[:-4] + ".jpg"
+    return path
+
+
+def write_images(paths, images_u8):
+    """write_pngs by the selected format (set_image_format): image i goes to image_path(paths[i]).  Returns the paths actually written."""
+    paths = list(paths)
+    name, quality, subsampling = _image_format
+    if name == "png":
+        write_pngs(paths, images_u8)
+        return paths
+    if len(paths) != images_u8.shape[0]:
+        raise ValueError("write_images: %d paths for %d images" % (len(paths), images_u8.shape[0]))
+    written = [image_path(p) for p in paths]
+    for path, blob in zip(written, ops.jpeg_encode(images_u8.contiguous(), quality, subsampling)):
+        with open(path, "wb") as f:
+            f.write(blob)
+    return written
+
+
 def _as_stack(img):
     if img.dtype != torch.uint8:
         raise TypeError("metrics take uint8 HWC / BHWC images (to_uint8_image)")
@@ -359,7 +407,11 @@ def run_test(G, loader, save_dir=None, tag="0.00", metrics=True, nima=None, suff
 
     nima: a `uegan_amd.nima.NIMA` module -> also "nima" / "nima_std" (per image) and "mean_nima" (true mean): what calc_nima (tester.py:91-94,
     on by default in the reference: config.py:80) computes from the saved files, here from the same 8-bit images on the device.  It needs no
-    label: with metrics=False the loader's `img_exp` is never touched (the unpaired setting)."""
+    label: with metrics=False the loader's `img_exp` is never touched (the unpaired setting).
+
+    The files go through `write_images`: with set_image_format("jpeg", ...) they are baseline JPEGs named `.jpg` instead of `.png`.  NIMA, PSNR and
+    SSIM are computed from the device's 8-bit tensor BEFORE it is encoded, whatever the format: with JPEG the numbers describe the enhanced
+    pixels, not the lossy file, and equal those of a PNG run."""
     rec = _TestRecord(metrics, nima, save_dir, compare_dir, tag, suffix, compare_suffix)
     for batch in loader:
         if isinstance(batch.img_raw, (list, tuple)):      # native mode: the samples one by one, since their sizes may differ
@@ -410,7 +462,7 @@ class _TestRecord:
         self.names += names
         for (d, suffix), images in zip(self.dirs, (q, pair)):
             if d is not None and images is not None:
-                write_pngs([os.path.join(d, "%s_%s_%s.png" % (name, self.tag, suffix)) for name in names], images)
+                write_images([os.path.join(d, "%s_%s_%s.png" % (name, self.tag, suffix)) for name in names], images)
 
     def result(self):
         out = {"names": self.names, "psnr": self.psnr, "ssim": self.ssim}
