@@ -55,8 +55,10 @@ static RedPlan make_plan(int B, int HW, int C, int dtype) {
   while ((long)B * p.ncg * s < kGridTarget && s < 2048 && HW / (2 * s) >= 128) s *= 2;
   // ... and, on the small maps of the attention modules (<= 64 x 64: ga4 / ga5 of a 512^2 input), down to 16 pixels while ONE image's blocks are a fraction
   // of the chip: at batch 1 these were 8 / 32 blocks whose threads walked 32 / 16 dependent loads (moments 9.7 / 8.5 us, apply 8.7 / 5.4 us for 1 MB).
-  // Per image, not per batch: the split count of a map must not depend on how many images share the launch (Generator.forward_pair is bit-identical to
-  // two passes, tests/test_fused.py)
+  // Per image, not per batch: on these maps (at most 4096 pixels; fewer than 8 channel groups, i.e. every layer of the model -- with more, the loop above
+  // can outrun this one) the split count does not depend on how many images share the launch, so a pair pass and two single passes are bit-identical there
+  // (Generator.forward_pair, tests/test_fused.py; tests/test_reduction_kernels.py pins the range).  Above 4096 pixels S follows B * ncg (the loop above
+  // and `cap`): a batch and its images alone then sum in different orders and agree to rounding only.
   while (HW <= 4096 && (long)p.ncg * s < 128 && s < 2048 && HW / (2 * s) >= 16) s *= 2;
   p.chunk = (HW + s - 1) / s;
   p.S = (HW + p.chunk - 1) / p.chunk;
