@@ -422,6 +422,26 @@ int uegan_jpeg_encode(const uint8_t* images, int B, int H, int W, int quality, i
 /* Stage 1 alone: the quantised coefficients, DEVICE int16 [B][component][block row][block col][64] in zigzag order (4:2:0: the Y plane has
  * 2 x 2 blocks per MCU, so the three planes of an image differ in size; every plane covers whole MCUs). */
 int uegan_jpeg_coeffs(const uint8_t* images, int B, int H, int W, int quality, int subsampling, int16_t* coeffs, uegan_stream_t stream);
+/* OPTIMISED HUFFMAN TABLES (opt-in).  The files above carry the Annex K.3 tables, which were made for quality 75; with flags bit 0 set every file
+ * carries its OWN four tables instead, built on the device from that image's symbol counts by Annex K.2 exactly as libjpeg's
+ * jpeg_gen_optimal_table does it (frequency 1 for a reserved 257th symbol so that no code is all ones; the two least frequencies merged, ties
+ * to the largest index; lengths above 16 moved up pairwise; HUFFVAL by length, then symbol).  A table holds only the symbols that occur, so the
+ * four DHT segments and with them the header shrink: 281 + the four symbol counts bytes, at most 629.  Same coefficients, same pixels after
+ * decoding, same marker order; smaller files.  An own table may give a DC category a 16-bit code (K.3: 11), so a block takes up to
+ * 16 + 11 + 63 x 26 bits and the capacity and the workspace of this mode are a little larger: ask the _ex functions with the same flags.
+ * flags == 0 is uegan_jpeg_encode / _capacity_bytes / _workspace_bytes to the byte; any other bit than 0 is UEGAN_E_INVALID (the sizes: 0).
+ * The two steps of a split call take the same flags. */
+int uegan_jpeg_encode_ex(const uint8_t* images, int B, int H, int W, int quality, int subsampling, int flags, uint8_t* out, int64_t out_stride,
+                         int64_t* sizes, void* workspace, uegan_stream_t stream);
+size_t uegan_jpeg_capacity_bytes_ex(int H, int W, int subsampling, int flags);
+size_t uegan_jpeg_workspace_bytes_ex(int B, int H, int W, int subsampling, int flags);
+/* The statistics pass alone.  coeffs: DEVICE, as uegan_jpeg_coeffs leaves them -> hist: DEVICE uint64 [B][4][256], how often the entropy coder
+ * emits each symbol of each table; tables in the order DC luma, DC chroma, AC luma, AC chroma (ZRL and EOB count as AC symbols 0xF0 and 0x00). */
+int uegan_jpeg_histogram(const int16_t* coeffs, int B, int H, int W, int subsampling, uint64_t* hist, uegan_stream_t stream);
+/* The code construction alone, on any counts.  hist: DEVICE uint64 [n][4][256] -> dht: DEVICE uint8 [n][4][16 + 256], per table the 16 BITS
+ * counts, then HUFFVAL, zero-filled behind it; codes: DEVICE uint32 [n][4][256], per symbol length << 16 | code of the canonical assignment, 0
+ * for a symbol that does not occur.  One symbol: a single 1-bit code 0.  No symbol: everything 0.  1 <= n <= 65535. */
+int uegan_jpeg_build_tables(const uint64_t* hist, int n, uint8_t* dht, uint32_t* codes, uegan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Input pipeline on the device (data_loader.py:74-82 train transform, :95-100 test transform, :126 H2D)

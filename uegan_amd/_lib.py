@@ -170,6 +170,11 @@ SIGNATURES = {
     "uegan_jpeg_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "uegan_jpeg_encode": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "uegan_jpeg_coeffs": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "uegan_jpeg_encode_ex": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "uegan_jpeg_capacity_bytes_ex": (c_sz, [c_int, c_int, c_int, c_int]),
+    "uegan_jpeg_workspace_bytes_ex": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    "uegan_jpeg_histogram": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "uegan_jpeg_build_tables": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
     "uegan_native_input":(c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),

@@ -39,8 +39,9 @@ static void prof_kernel_name(int key, char* buf, size_t n) {
     return;
   }
   if (key & PROF_JPEG) {
-    static const char* const jpeg[] = {"jpeg_tables_kernel", "jpeg_coeffs_kernel", "jpeg_pack_kernel<size>", "jpeg_offsets_kernel", "jpeg_pack_kernel<write>"};
-    snprintf(buf, n, "%s", jpeg[(key & 7) < 5 ? (key & 7) : 0]);
+    static const char* const jpeg[] = {"jpeg_tables_kernel", "jpeg_coeffs_kernel", "jpeg_pack_kernel<size>", "jpeg_offsets_kernel", "jpeg_pack_kernel<write>",
+                                       "jpeg_stats_kernel", "jpeg_build_kernel"};
+    snprintf(buf, n, "%s", jpeg[(key & 7) < 7 ? (key & 7) : 0]);
     return;
   }
   const int kind = (key >> 28) & 7, bn = (key >> 12) & 0xfff, ks = (key >> 8) & 15, mode = (key >> 4) & 15;

@@ -1467,9 +1467,18 @@ def jpeg_qtables(quality):
     return list(buf)
 
 
-def jpeg_capacity(H, W, subsampling="4:4:4"):
-    """bytes no file of this shape can exceed (uegan_jpeg_capacity_bytes: every code at its longest, every byte stuffed)"""
-    return int(lib().uegan_jpeg_capacity_bytes(H, W, JPEG_SUBSAMPLINGS[subsampling]))
+def _jpeg_flags(optimize, what):
+    """optimize -> the flags of the _ex entry points (bit 0: the image's own Huffman tables); only a bool is taken"""
+    if not isinstance(optimize, bool):
+        raise ValueError("%s: optimize %r is not a bool" % (what, optimize))
+    return 1 if optimize else 0
+
+
+def jpeg_capacity(H, W, subsampling="4:4:4", optimize=False):
+    """bytes no file of this shape can exceed (uegan_jpeg_capacity_bytes: every code at its longest, every byte stuffed; optimize: an own DC table
+    may hold a 16-bit code where the standard ones stop at 11, so the bound is a little larger)"""
+    flags = _jpeg_flags(optimize, "jpeg_capacity")
+    return int(lib().uegan_jpeg_capacity_bytes_ex(H, W, JPEG_SUBSAMPLINGS[subsampling], flags))
 
 
 def jpeg_coeffs(images_u8, quality=95, subsampling="4:4:4"):
@@ -1490,47 +1499,79 @@ def jpeg_coeffs(images_u8, quality=95, subsampling="4:4:4"):
     return planes
 
 
-def _jpeg_sizing(images_u8, B, H, W, q, ss):
+def jpeg_histogram(images_u8, quality=95, subsampling="4:4:4"):
+    """the statistics pass of the optimised mode alone (uegan_jpeg_coeffs, then uegan_jpeg_histogram): how often the entropy coder emits each symbol
+    of each table for these images -> int64 device tensor [B, 4, 256], tables in the order DC luma, DC chroma, AC luma, AC chroma"""
+    B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_histogram")
+    _chk(images_u8)
+    flat = torch.cat([p.reshape(B, -1) for p in jpeg_coeffs(images_u8, quality, subsampling)], dim=1).contiguous()
+    hist = torch.empty((B, 4, 256), dtype=torch.int64, device=images_u8.device)
+    L.check(lib().uegan_jpeg_histogram(flat.data_ptr(), B, H, W, ss, hist.data_ptr(), _stream()))
+    return hist
+
+
+def jpeg_build_tables(hist):
+    """the code construction of the optimised mode alone (uegan_jpeg_build_tables: Annex K.2 as libjpeg's jpeg_gen_optimal_table) on any counts.
+    hist: int64 [n, 4, 256] on the device, counts >= 0 -> (dht uint8 [n, 4, 272]: per table the 16 BITS counts, then HUFFVAL, zero-filled;
+    codes int32 [n, 4, 256]: per symbol length << 16 | code, 0 for a symbol that does not occur)"""
+    if not torch.is_tensor(hist) or hist.dtype != torch.int64 or hist.dim() != 3 or tuple(hist.shape[1:]) != (4, 256) or not hist.is_contiguous():
+        raise TypeError("jpeg_build_tables expects a contiguous int64 [n, 4, 256] tensor")
+    n = hist.shape[0]
+    if not 1 <= n <= 65535:
+        raise ValueError("jpeg_build_tables: %d histogram sets (1..65535)" % n)
+    _chk(hist)
+    dht = torch.empty((n, 4, 272), dtype=torch.uint8, device=hist.device)
+    codes = torch.empty((n, 4, 256), dtype=torch.int32, device=hist.device)
+    L.check(lib().uegan_jpeg_build_tables(hist.data_ptr(), n, dht.data_ptr(), codes.data_ptr(), _stream()))
+    return dht, codes
+
+
+def _jpeg_sizing(images_u8, B, H, W, q, ss, flags=0):
     """the sizing step -> (sizes tensor, workspace): coefficients, code lengths and offsets stay in the workspace"""
     dev = images_u8.device
     sizes = torch.empty((B,), dtype=torch.int64, device=dev)
-    ws = torch.empty((lib().uegan_jpeg_workspace_bytes(B, H, W, ss),), dtype=torch.uint8, device=dev)
-    L.check(lib().uegan_jpeg_encode(images_u8.data_ptr(), B, H, W, q, ss, None, 0, sizes.data_ptr(), ws.data_ptr(), _stream()))
+    ws = torch.empty((lib().uegan_jpeg_workspace_bytes_ex(B, H, W, ss, flags),), dtype=torch.uint8, device=dev)
+    L.check(lib().uegan_jpeg_encode_ex(images_u8.data_ptr(), B, H, W, q, ss, flags, None, 0, sizes.data_ptr(), ws.data_ptr(), _stream()))
     return sizes, ws
 
 
-def jpeg_sizes(images_u8, quality=95, subsampling="4:4:4"):
+def jpeg_sizes(images_u8, quality=95, subsampling="4:4:4", optimize=False):
     """the exact sizes of the files jpeg_encode would return, without writing them (the sizing step of uegan_jpeg_encode) -> list of B ints"""
     B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_sizes")
+    flags = _jpeg_flags(optimize, "jpeg_sizes")
     _chk(images_u8)
-    return [int(v) for v in _jpeg_sizing(images_u8, B, H, W, q, ss)[0].tolist()]
+    return [int(v) for v in _jpeg_sizing(images_u8, B, H, W, q, ss, flags)[0].tolist()]
 
 
-def jpeg_encode(images_u8, quality=95, subsampling="4:4:4", out=None):
+def jpeg_encode(images_u8, quality=95, subsampling="4:4:4", out=None, optimize=False):
     """uint8 [B,H,W,3] on the device -> B complete baseline JPEG files as bytes (uegan_jpeg_encode: JFIF YCbCr, fp32 DCT, the Annex K tables, one
     restart interval per MCU row), every per-pixel and per-bit step on the device.  The capacity bound of a shape is far above what a photograph
     takes, so the call is split: the sizing step leaves the exact file sizes on the device, the host reads them, allocates exactly that and runs
     the writing step; then one D2H copy of the files.  out: a uint8 device tensor [B, stride] with stride >= jpeg_capacity(H, W, subsampling) to
     encode into in ONE call instead (the files are returned all the same; bytes of `out` behind a file are left as they were).
     Refused before any launch: anything but a contiguous uint8 [B,H,W,3] tensor (TypeError); an empty batch, a quality outside 1..100, a subsampling
-    other than "4:4:4" / "4:2:0", a side above 65535 (ValueError)."""
+    other than "4:4:4" / "4:2:0", a side above 65535, an optimize that is not a bool (ValueError).
+    optimize=True (uegan_jpeg_encode_ex, flags bit 0): every file carries its own four Huffman tables, built on the device from that image's symbol
+    counts the way libjpeg's optimize does -- the same coefficients and decoded pixels in a smaller file; `out` then needs
+    jpeg_capacity(H, W, subsampling, optimize=True).  False: the Annex K.3 tables, every byte as before."""
     B, H, W, q, ss = _jpeg_args(images_u8, quality, subsampling, "jpeg_encode")
+    flags = _jpeg_flags(optimize, "jpeg_encode")
     dev = images_u8.device
     if out is not None:
-        cap = lib().uegan_jpeg_capacity_bytes(H, W, ss)
+        cap = lib().uegan_jpeg_capacity_bytes_ex(H, W, ss, flags)
         if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < cap or not out.is_contiguous() \
                 or out.device != dev:
             raise TypeError("jpeg_encode: out must be a contiguous uint8 [%d, >= %d] tensor on the images' device" % (B, cap))
         _chk(images_u8, out)
         stride = out.shape[1]
         sizes = torch.empty((B,), dtype=torch.int64, device=dev)
-        ws = torch.empty((lib().uegan_jpeg_workspace_bytes(B, H, W, ss),), dtype=torch.uint8, device=dev)
-        L.check(lib().uegan_jpeg_encode(images_u8.data_ptr(), B, H, W, q, ss, out.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
+        ws = torch.empty((lib().uegan_jpeg_workspace_bytes_ex(B, H, W, ss, flags),), dtype=torch.uint8, device=dev)
+        L.check(lib().uegan_jpeg_encode_ex(images_u8.data_ptr(), B, H, W, q, ss, flags, out.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
         return _png_fetch(out.view(-1), stride, sizes)
     _chk(images_u8)
-    sizes, ws = _jpeg_sizing(images_u8, B, H, W, q, ss)
+    sizes, ws = _jpeg_sizing(images_u8, B, H, W, q, ss, flags)
     known = [int(v) for v in sizes.tolist()]
-    stride = (max(known) + 15) // 16 * 16
+    stride = max((max(known) + 15) // 16 * 16, 640)          # (the C entry asks for room for the longest header, whatever this one's length)
     buf = torch.empty((B * stride,), dtype=torch.uint8, device=dev)
-    L.check(lib().uegan_jpeg_encode(None, B, H, W, q, ss, buf.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
+    L.check(lib().uegan_jpeg_encode_ex(None, B, H, W, q, ss, flags, buf.data_ptr(), stride, sizes.data_ptr(), ws.data_ptr(), _stream()))
     return _png_fetch(buf, stride, known)

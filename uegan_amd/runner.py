@@ -18,7 +18,8 @@ What differs from the reference, on purpose:
     sample draws never shifts the training data.
   * UEGAN_PNG_ENCODER=device in the environment: samples, validation and test images are encoded on the device (tester.write_pngs); same pixels.
   * UEGAN_IMAGE_FORMAT=jpeg (with UEGAN_JPEG_QUALITY=1..100, default 95) in the environment: those files are baseline JPEGs named .jpg, encoded on
-    the device (tester.write_images); the metrics are computed before encoding and equal those of a PNG run.
+    the device (tester.write_images); the metrics are computed before encoding and equal those of a PNG run.  UEGAN_JPEG_OPTIMIZE=1 with it:
+    every file carries its own Huffman tables (smaller files, the same pixels after decoding).
   * a step that prints nothing reads nothing from the device: the five losses are fetched (Trainer.loss_items) every --info_step only.
 """
 import json
@@ -302,13 +303,15 @@ def _apply_png_encoder():
 
 IMAGE_FORMAT_ENV = "UEGAN_IMAGE_FORMAT"
 JPEG_QUALITY_ENV = "UEGAN_JPEG_QUALITY"
+JPEG_OPTIMIZE_ENV = "UEGAN_JPEG_OPTIMIZE"
 
 
 def _apply_image_format():
-    """UEGAN_IMAGE_FORMAT=png|jpeg in the environment selects the container of every image the run writes (tester.set_image_format), and
-    UEGAN_JPEG_QUALITY=1..100 the quality of "jpeg" (default 95); unset: the selection stays (default "png").  Any other value is refused by name,
-    and so is a quality without UEGAN_IMAGE_FORMAT=jpeg.  They are not flags: the flag set is the reference's."""
-    name, quality = os.environ.get(IMAGE_FORMAT_ENV), os.environ.get(JPEG_QUALITY_ENV)
+    """UEGAN_IMAGE_FORMAT=png|jpeg in the environment selects the container of every image the run writes (tester.set_image_format),
+    UEGAN_JPEG_QUALITY=1..100 the quality of "jpeg" (default 95) and UEGAN_JPEG_OPTIMIZE=0|1 whether its files carry their own Huffman tables
+    (default 0); unset: the selection stays (default "png").  Any other value is refused by name, and so is a quality or an optimize=1 without
+    UEGAN_IMAGE_FORMAT=jpeg.  They are not flags: the flag set is the reference's."""
+    name, quality, optimize = os.environ.get(IMAGE_FORMAT_ENV), os.environ.get(JPEG_QUALITY_ENV), os.environ.get(JPEG_OPTIMIZE_ENV)
     if name is not None and name not in tester.IMAGE_FORMATS:
         raise ValueError("%s=%r: expected one of %s" % (IMAGE_FORMAT_ENV, name, ", ".join(tester.IMAGE_FORMATS)))
     if quality is not None:
@@ -316,8 +319,13 @@ def _apply_image_format():
             raise ValueError("%s=%r needs %s=jpeg" % (JPEG_QUALITY_ENV, quality, IMAGE_FORMAT_ENV))
         if not (quality.isascii() and quality.isdigit() and 1 <= int(quality) <= 100):
             raise ValueError("%s=%r: expected an integer in [1, 100]" % (JPEG_QUALITY_ENV, quality))
+    if optimize is not None:
+        if optimize not in ("0", "1"):
+            raise ValueError("%s=%r: expected 0 or 1" % (JPEG_OPTIMIZE_ENV, optimize))
+        if optimize == "1" and name != "jpeg":
+            raise ValueError("%s=%r needs %s=jpeg" % (JPEG_OPTIMIZE_ENV, optimize, IMAGE_FORMAT_ENV))
     if name == "jpeg":
-        tester.set_image_format("jpeg", quality=int(quality) if quality is not None else 95)
+        tester.set_image_format("jpeg", quality=int(quality) if quality is not None else 95, optimize=optimize == "1")
     elif name == "png":
         tester.set_image_format("png")
 

@@ -17,7 +17,8 @@
     write_pngs(paths, images_u8)      the 8-bit images as PNG files, by the encoder set_png_encoder selects: "pillow" (the default: Image.save on the
                                       host) or "device" (ops.png_encode: filter, deflate and CRCs in libuegan_hip.so, the host only writes)
     write_images(paths, images_u8)    ... by the format set_image_format selects: "png" (write_pngs, the default) or "jpeg" (ops.jpeg_encode: baseline
-                                      JPEG on the device, files named .jpg); returns the paths written
+                                      JPEG on the device, files named .jpg; set_image_format(optimize=True): with the image's own Huffman
+                                      tables); returns the paths written
     run_test(G, loader, ...)          the loop of Tester.test (tester.py:40-105): enhance every batch of a test loader, write the
                                       PNGs `save_image` would write, PSNR / SSIM against the labels on the device, and the NIMA
                                       score of the enhanced images (uegan_amd/nima.py) when a scorer is passed
@@ -295,25 +296,38 @@ def write_pngs(paths, images_u8):
 
 IMAGE_FORMATS = ("png", "jpeg")
 _image_format = ("png", 95, "4:4:4")
+_jpeg_optimize = False
 
 
-def set_image_format(name, quality=95, subsampling="4:4:4"):
+def set_image_format(name, quality=95, subsampling="4:4:4", optimize=False):
     """the container write_images writes: "png" (the default: write_pngs, every file name and byte as before) or "jpeg" (ops.jpeg_encode with this
     quality, 1..100, and subsampling, "4:4:4" or "4:2:0": baseline JPEG files named .jpg, always encoded on the device -- there is no Pillow arm,
-    and the PNG encoder selection does not matter to it).  Anything else: ValueError, and the selection stays."""
-    global _image_format
+    and the PNG encoder selection does not matter to it).  optimize (a bool; "jpeg" only): every file carries its own Huffman tables, built on the
+    device from its symbol counts, instead of the standard ones: the same pixels in a smaller file.  Anything else: ValueError, and the selection
+    stays."""
+    global _image_format, _jpeg_optimize
     if name not in IMAGE_FORMATS:
         raise ValueError("unknown image format %r (one of %s)" % (name, ", ".join(IMAGE_FORMATS)))
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
         raise ValueError("JPEG quality %r is not an integer in [1, 100]" % (quality,))
     if subsampling not in ops.JPEG_SUBSAMPLINGS:
         raise ValueError("JPEG subsampling %r is not one of %s" % (subsampling, ", ".join(ops.JPEG_SUBSAMPLINGS)))
+    if not isinstance(optimize, bool):
+        raise ValueError("JPEG optimize %r is not a bool" % (optimize,))
+    if optimize and name != "jpeg":
+        raise ValueError("optimize=True needs the \"jpeg\" format, not %r" % (name,))
     _image_format = (name, quality, subsampling)
+    _jpeg_optimize = optimize
 
 
 def get_image_format():
     """(name, quality, subsampling) as set_image_format took them; quality and subsampling only matter to the "jpeg" format"""
     return _image_format
+
+
+def get_jpeg_optimize():
+    """whether write_images asks the "jpeg" format for per-image Huffman tables (set_image_format's optimize; False after any other selection)"""
+    return _jpeg_optimize
 
 
 def image_path(path):
@@ -333,7 +347,7 @@ def write_images(paths, images_u8):
     if len(paths) != images_u8.shape[0]:
         raise ValueError("write_images: %d paths for %d images" % (len(paths), images_u8.shape[0]))
     written = [image_path(p) for p in paths]
-    for path, blob in zip(written, ops.jpeg_encode(images_u8.contiguous(), quality, subsampling)):
+    for path, blob in zip(written, ops.jpeg_encode(images_u8.contiguous(), quality, subsampling, optimize=_jpeg_optimize)):
         with open(path, "wb") as f:
             f.write(blob)
     return written
