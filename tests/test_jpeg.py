@@ -548,7 +548,7 @@ def test_refusals(monkeypatch):
 
     def reached(*a, **k):
         raise AssertionError("a refusal must come before the library is reached")
-    monkeypatch.setattr(ops, "lib", reached)
+    monkeypatch.setattr(_lib, "load", reached)
     ok = torch.zeros((1, 4, 5, 3), dtype=torch.uint8)
     for fn in (ops.jpeg_encode, ops.jpeg_sizes, ops.jpeg_coeffs):
         for bad in (ok.float(), ok[0], torch.zeros((1, 4, 5, 4), dtype=torch.uint8), torch.zeros((1, 4, 3, 5), dtype=torch.uint8).permute(0, 1, 3, 2),

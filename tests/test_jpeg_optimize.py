@@ -411,7 +411,7 @@ def test_refusals(monkeypatch):
 
     def reached(*a, **k):
         raise AssertionError("a refusal must come before the library is reached")
-    monkeypatch.setattr(ops, "lib", reached)
+    monkeypatch.setattr(_lib, "load", reached)
     ok = torch.zeros((1, 4, 5, 3), dtype=torch.uint8)
     for bad in (1, 0, None, "1", 1.0):
         for fn in (ops.jpeg_encode, ops.jpeg_sizes):

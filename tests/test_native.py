@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from helpers import BACKENDS, use_backend
 from oracle import uegan_oracle as O
 from test_montage import _images
-from uegan_amd import data, models, ops, runner, tester
+from uegan_amd import _lib, data, models, ops, runner, tester
 
 
 def _pixels(seed, B, h, w):
@@ -158,14 +158,13 @@ def test_montage_crop_past_the_grid_cap(src, window):
 def test_native_refusals(backend, monkeypatch):
     dev = use_backend(backend)
     launched = []
-    real = ops.lib
+    real = _lib.load
 
     class _Spy:
         def __getattr__(self, name):
             launched.append(name)
             return getattr(real(), name)
-    monkeypatch.setattr(ops, "lib", lambda: _Spy())
-    monkeypatch.setattr(data, "lib", lambda: _Spy())
+    monkeypatch.setattr(_lib, "load", lambda *a, **k: _Spy())
     G = models.Generator(8, "none", "LeakyReLU", False)
     for shape in ((1, 31, 48), (1, 48, 31)):
         pix = torch.zeros(shape + (3,), dtype=torch.uint8, device=dev)

@@ -1,4 +1,4 @@
-"""Kernel-level parity: every C-ABI op (through the autograd wrappers in uegan_amd/ops.py) against plain PyTorch fp32 /
+"""Kernel-level parity: every C-ABI op (through the autograd wrappers in uegan_amd/ops/) against plain PyTorch fp32 /
 the CPU oracle on identical seeded inputs.  Each test runs on the CPU fiber emulator (`-m "not gpu"`) and on the
 MI355X (`-m gpu`).  Tolerances: fp32 path 2e-5 relative-to-max (accumulation order only); bf16 storage 2e-2
 against a reference evaluated on bf16-rounded operands.
@@ -1145,11 +1145,12 @@ POOL_CASES = [
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", POOL_CASES, ids=lambda c: "x".join(map(str, c)))
-def test_conv_fwd_with_fused_maxpool(backend, dtype, case, monkeypatch):
+def test_conv_fwd_with_fused_maxpool(backend, dtype, case, request):
     import ctypes
     set_tuning("SMALL_GRID", 0)
     # (the unfused launch this compares with bit for bit must sum its K loop in the same order: no split-K on these emulator-sized grids)
-    monkeypatch.setattr(ops, "split_k", [False])
+    request.addfinalizer(lambda was=ops.split_k[0]: ops.split_k.__setitem__(0, was))
+    ops.split_k[0] = False      # (edited in place: the flag's readers hold the list, whatever name they reached it by)
     dev = use_backend(backend)
     lib = _lib.load()
     B, Cc, H, W, Co = case

@@ -27,7 +27,7 @@ from helpers import BACKENDS, use_backend
 from oracle import uegan_oracle as O
 from test_montage import _images
 from test_native import _photo, _png, _tree
-from uegan_amd import data, models, ops, tester
+from uegan_amd import _lib, data, models, ops, tester
 
 _RECORD = {"window_moments": {}, "end_to_end": {}}
 
@@ -563,14 +563,13 @@ def test_tiled_refusals(backend, monkeypatch):
     pix = torch.zeros(1, 64, 96, 3, dtype=torch.uint8, device=dev)
     moments = [torch.zeros(2, 1, 8 << k, device=dev) for k in range(5)]
     launched = []
-    real = ops.lib
+    real = _lib.load
 
     class _Spy:
         def __getattr__(self, name):
             launched.append(name)
             return getattr(real(), name)
-    monkeypatch.setattr(ops, "lib", lambda: _Spy())
-    monkeypatch.setattr(data, "lib", lambda: _Spy())
+    monkeypatch.setattr(_lib, "load", lambda *a, **k: _Spy())
     tile = models.Tile(0, 0, 64, 96, moments)
     G.eval()
     with pytest.raises(RuntimeError, match="no_grad"):          # eval mode, gradients enabled

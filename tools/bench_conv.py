@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from uegan_amd import _lib as L, ops  # noqa: E402
+from uegan_amd.ops import conv, core  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--dtype", default="bf16")
@@ -91,7 +92,7 @@ for (name, H, C1, C2, Co, k, s, pm, act, nf, nd, nw) in LAYERS:
     w = (torch.randn(Co, C1 + C2, k, k, device=dev) * 0.05)
     b = torch.zeros(Co, device=dev)
     cfg_ = ops.ConvCfg(s, pm, act)
-    d = ops._desc(x1, x2, w, cfg_)
+    d = conv._desc(x1, x2, w, cfg_)
     ohwi, ihwo = cfg_.packed.get(w, dt, d.C1 + d.C2, d.Cout)
     y = torch.empty(B, d.Ho, d.Wo, d.Cout, device=dev, dtype=dt)
     dz = torch.randn(B, d.Ho, d.Wo, d.Cout, device=dev).to(dt)
@@ -102,7 +103,7 @@ for (name, H, C1, C2, Co, k, s, pm, act, nf, nd, nw) in LAYERS:
     dw = torch.empty_like(w)
     db = torch.empty(Co, device=dev)
     st = torch.cuda.current_stream().cuda_stream
-    p = ops._p
+    p = core._p
     flops = 2.0 * B * d.Ho * d.Wo * Co * k * k * (C1 + C2)
     tf = timeit(lambda: L.check(lib.uegan_conv2d_fwd(C.byref(d), p(x1), p(x2), p(ohwi), p(b), None, p(y), st)), args.iters)
     dwsb = lib.uegan_conv2d_dgrad_workspace_bytes(C.byref(d))

@@ -9,6 +9,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import uegan_amd  # noqa: E402
 from uegan_amd import ops  # noqa: E402
+from uegan_amd.ops import core  # noqa: E402
 
 uegan_amd.set_compute_dtype(torch.bfloat16)
 dev = torch.device("cuda:0")
@@ -31,9 +32,9 @@ def timeit(fn, iters=5):
 x = torch.randn(B, H, W, C, device=dev).to(dt)
 y = torch.randn(B, H, W, C, device=dev).to(dt)
 nb = x.numel() * 2
-lib = ops.lib()
+lib = core.lib()
 st = torch.cuda.current_stream().cuda_stream
-p = ops._p
+p = core._p
 out = torch.empty_like(x)
 out2 = torch.empty_like(x)
 from uegan_amd import _lib as L  # noqa: E402

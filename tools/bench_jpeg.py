@@ -2,8 +2,8 @@
 """Time the ways an 8-bit image stack on the device becomes image files in memory, the arms alternating in one process (cf. bench_png.py):
 
     (a) pillow   images.cpu().numpy() + Pillow's Image.save(format="JPEG", quality=q, subsampling=...) into a BytesIO per image
-    (b) device   ops.jpeg_encode(images, q, subsampling): sizing step, read of the sizes, writing step, D2H copy of the files
-    (c) png      ops.png_encode(images) of the same pixels: what the device wrote before there was a JPEG mode
+    (b) device   codecs.jpeg_encode(images, q, subsampling): sizing step, read of the sizes, writing step, D2H copy of the files
+    (c) png      codecs.png_encode(images) of the same pixels: what the device wrote before there was a JPEG mode
     (d) device, optimize=True   every file with its own Huffman tables (two more launches: jpeg_stats_kernel, jpeg_build_kernel)
     (e) pillow, optimize=True   libjpeg's own two-pass optimisation of the same pixels
 
@@ -31,7 +31,7 @@ from PIL import Image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from uegan_amd import _lib, ops  # noqa: E402
+from uegan_amd import _lib, codecs  # noqa: E402
 
 SIZES = [(512, 512, 1), (512, 1536, 16), (2048, 4096, 1), (4096, 6144, 1)]      # h, w, batch
 PILLOW_SS = {"4:4:4": 0, "4:2:0": 2}
@@ -63,11 +63,11 @@ def wall_ms(fn):
 
 
 def launches(images, quality, ss, calls, optimize=False):
-    """ms per launch of ops.jpeg_encode's kernels from the library's event records, mean over `calls` calls"""
+    """ms per launch of codecs.jpeg_encode's kernels from the library's event records, mean over `calls` calls"""
     lib = _lib.load()
     _lib.check(lib.uegan_profile_begin(8 * calls))
     for _ in range(calls):
-        ops.jpeg_encode(images, quality, ss, optimize=optimize)
+        codecs.jpeg_encode(images, quality, ss, optimize=optimize)
     entries = (_lib.ProfileEntry * 16)()
     n = ctypes.c_int(0)
     _lib.check(lib.uegan_profile_end(entries, 16, ctypes.byref(n)))
@@ -85,24 +85,24 @@ def main():
         raise SystemExit("bench_jpeg.py needs a GPU")
     dev = torch.device("cuda:0")
     q = args.quality
-    out = {"what": "8-bit images on the device -> image files in host memory: Pillow's JPEG save on the host vs ops.jpeg_encode vs ops.png_encode, wall-clock "
+    out = {"what": "8-bit images on the device -> image files in host memory: Pillow's JPEG save on the host vs codecs.jpeg_encode vs codecs.png_encode, wall-clock "
                    "ms per image (sorted, one value per alternating window)", "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "quality": q,
            "sizes": {}}
     for spec in args.sizes.split(","):
         h, w, b = (int(v) for v in spec.split("x"))
         images = photo(1990 + h, b, h, w).to(dev)
-        png_files = ops.png_encode(images)                      # (warm-up of the device arms; Pillow needs none)
+        png_files = codecs.png_encode(images)                      # (warm-up of the device arms; Pillow needs none)
         rec = {"batch": b, "png_file_bytes": sum(len(f) for f in png_files)}
         t_png = []
         for ss in PILLOW_SS:
-            files = ops.jpeg_encode(images, q, ss)
+            files = codecs.jpeg_encode(images, q, ss)
             ref = pillow_arm(images, q, ss)
             for i in (0, b - 1):
                 src = images[i].cpu().numpy().astype(int)
                 with Image.open(io.BytesIO(files[i])) as im, Image.open(io.BytesIO(ref[i])) as want:
                     err, err_ref = np.abs(np.array(im).astype(int) - src).mean(), np.abs(np.array(want).astype(int) - src).mean()
                     assert im.size == (w, h) and err <= err_ref + 0.1, "the device's file is further from its image than Pillow's: %.3f vs %.3f levels" % (err, err_ref)
-            files_opt = ops.jpeg_encode(images, q, ss, optimize=True)
+            files_opt = codecs.jpeg_encode(images, q, ss, optimize=True)
             ref_opt = pillow_arm(images, q, ss, True)
             for i in (0, b - 1):                                    # own tables: other bytes, the same pixels
                 with Image.open(io.BytesIO(files[i])) as im, Image.open(io.BytesIO(files_opt[i])) as im_opt:
@@ -110,11 +110,11 @@ def main():
             t_host, t_dev, t_host_opt, t_dev_opt = [], [], [], []
             for _ in range(args.rounds):
                 t_host.append(wall_ms(lambda: pillow_arm(images, q, ss)) / b)
-                t_dev.append(wall_ms(lambda: ops.jpeg_encode(images, q, ss)) / b)
+                t_dev.append(wall_ms(lambda: codecs.jpeg_encode(images, q, ss)) / b)
                 t_host_opt.append(wall_ms(lambda: pillow_arm(images, q, ss, True)) / b)
-                t_dev_opt.append(wall_ms(lambda: ops.jpeg_encode(images, q, ss, optimize=True)) / b)
+                t_dev_opt.append(wall_ms(lambda: codecs.jpeg_encode(images, q, ss, optimize=True)) / b)
                 if ss == "4:4:4":
-                    t_png.append(wall_ms(lambda: ops.png_encode(images)) / b)
+                    t_png.append(wall_ms(lambda: codecs.png_encode(images)) / b)
             t_host.sort()
             t_dev.sort()
             spread = max(t_host[-1] - t_host[0], t_dev[-1] - t_dev[0])
@@ -148,7 +148,7 @@ def main():
     # the images tests/test_jpeg.py::test_size_against_pillow bounds (same generator, same seeds); its bound is the 96 x 128 ratio + 0.02
     for h, w in ((96, 128), (512, 512), (1024, 1536)):
         images = photo(60 + h % 7, 1, h, w).to(dev)
-        out["size_ratio_%dx%d" % (h, w)] = {"q%d %s" % (quality, ss): round(len(ops.jpeg_encode(images, quality, ss)[0]) / len(pillow_arm(images, quality, ss)[0]), 4)
+        out["size_ratio_%dx%d" % (h, w)] = {"q%d %s" % (quality, ss): round(len(codecs.jpeg_encode(images, quality, ss)[0]) / len(pillow_arm(images, quality, ss)[0]), 4)
                                             for quality in (90, 95) for ss in PILLOW_SS}
     # the images tests/test_jpeg_optimize.py::test_optimized_is_smaller asks to shrink (same generator, same seeds), Pillow's own pair beside them
     for h, w in ((96, 128), (256, 384), (512, 512), (1024, 1536)):
@@ -156,7 +156,7 @@ def main():
         rec = {}
         for quality in (75, 95):
             for ss in PILLOW_SS:
-                std, opt = ops.jpeg_sizes(images, quality, ss)[0], ops.jpeg_sizes(images, quality, ss, optimize=True)[0]
+                std, opt = codecs.jpeg_sizes(images, quality, ss)[0], codecs.jpeg_sizes(images, quality, ss, optimize=True)[0]
                 rec["q%d %s" % (quality, ss)] = {"device": round(opt / std, 4),
                                                  "pillow": round(len(pillow_arm(images, quality, ss, True)[0]) / len(pillow_arm(images, quality, ss)[0]), 4)}
         out["optimize_ratio_%dx%d" % (h, w)] = rec

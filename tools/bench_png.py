@@ -2,7 +2,7 @@
 """Time the two ways an 8-bit image stack on the device becomes PNG files in memory, the two arms alternating in one process (cf. bench_native.py):
 
     (a) host     images.cpu().numpy() + Pillow's Image.save(format="png") into a BytesIO per image: what tester.write_pngs does by default
-    (b) device   ops.png_encode(images), including its read of the sizes and its D2H copy of the used bytes ("device" encoder)
+    (b) device   codecs.png_encode(images), including its read of the sizes and its D2H copy of the used bytes ("device" encoder)
 
 on photograph-shaped images (low-pass noise plus grain, as tests/test_native.py::_photo) at 512x512, 16 x 512x1536 (the sample montages of one training
 batch), 2048x4096 and 4096x6144.  Wall-clock ms per image after a synchronize (both arms end on the host), `--rounds` windows per arm, sorted.  Per
@@ -27,7 +27,7 @@ from PIL import Image
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from uegan_amd import _lib, ops  # noqa: E402
+from uegan_amd import _lib, codecs  # noqa: E402
 
 SIZES = [(512, 512, 1), (512, 1536, 16), (2048, 4096, 1), (4096, 6144, 1)]      # h, w, batch
 
@@ -58,11 +58,11 @@ def wall_ms(fn):
 
 
 def launches(images, calls):
-    """ms per launch of ops.png_encode's kernels from the library's event records, mean over `calls` calls"""
+    """ms per launch of codecs.png_encode's kernels from the library's event records, mean over `calls` calls"""
     lib = _lib.load()
     _lib.check(lib.uegan_profile_begin(8 * calls))
     for _ in range(calls):
-        ops.png_encode(images)
+        codecs.png_encode(images)
     entries = (_lib.ProfileEntry * 16)()
     n = ctypes.c_int(0)
     _lib.check(lib.uegan_profile_end(entries, 16, ctypes.byref(n)))
@@ -78,21 +78,21 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_png.py needs a GPU")
     dev = torch.device("cuda:0")
-    out = {"what": "8-bit images on the device -> PNG files in host memory: Pillow on the host vs ops.png_encode, wall-clock ms per image (sorted, one value "
+    out = {"what": "8-bit images on the device -> PNG files in host memory: Pillow on the host vs codecs.png_encode, wall-clock ms per image (sorted, one value "
                    "per alternating window)", "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "sizes": {}}
     for spec in args.sizes.split(","):
         h, w, b = (int(v) for v in spec.split("x"))
         images = photo(1990 + h, b, h, w).to(dev)
-        files = ops.png_encode(images)                      # (warm-up of the device arm; Pillow needs none)
+        files = codecs.png_encode(images)                      # (warm-up of the device arm; Pillow needs none)
         ref = pillow_arm(images)
         for i in (0, b - 1):
             with Image.open(io.BytesIO(files[i])) as im:
                 assert torch.equal(torch.from_numpy(np.array(im)), images[i].cpu()), "the device's file does not decode to its image"
-        ops.png_encode(images)
+        codecs.png_encode(images)
         t_host, t_dev = [], []
         for _ in range(args.rounds):
             t_host.append(wall_ms(lambda: pillow_arm(images)) / b)
-            t_dev.append(wall_ms(lambda: ops.png_encode(images)) / b)
+            t_dev.append(wall_ms(lambda: codecs.png_encode(images)) / b)
         t_host.sort()
         t_dev.sort()
         spread = max(t_host[-1] - t_host[0], t_dev[-1] - t_dev[0])
@@ -113,7 +113,7 @@ def main():
     out["size_ratio_on_the_test_images"] = {}
     for h, w in ((96, 128), (512, 512), (1024, 1536)):
         images = photo(60 + h % 7, 1, h, w).to(dev)
-        out["size_ratio_on_the_test_images"]["%dx%d" % (h, w)] = round(len(ops.png_encode(images)[0]) / len(pillow_arm(images)[0]), 4)
+        out["size_ratio_on_the_test_images"]["%dx%d" % (h, w)] = round(len(codecs.png_encode(images)[0]) / len(pillow_arm(images)[0]), 4)
     out["device_faster_at_every_size"] = all(r["device_faster_beyond_spread"] for r in out["sizes"].values())
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

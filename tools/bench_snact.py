@@ -6,10 +6,11 @@ sys.path.insert(0, ROOT)
 import torch
 import uegan_amd
 from uegan_amd import ops, _lib
+from uegan_amd.ops import core
 dev = torch.device("cuda:0")
 uegan_amd.set_compute_dtype(torch.bfloat16)
 lib = _lib.load()
-P = ops._p
+P = core._p
 for (H, C, pg, pg2) in [(256, 32, 3, 0), (256, 32, 0, 0), (128, 64, 3, 3), (128, 64, 0, 0), (64, 128, 3, 2), (64, 128, 0, 0), (32, 256, 2, 2), (32, 256, 0, 0), (16, 512, 2, 0), (16, 512, 0, 0)]:
     nb, ng = 16, 3
     B = nb * ng

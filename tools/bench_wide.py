@@ -6,6 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from uegan_amd import _lib as L, ops
+from uegan_amd.ops import conv, core
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=512)
 ap.add_argument("--hw", type=int, default=64)
@@ -30,11 +31,11 @@ for B in [int(v) for v in args.bs.split(",")]:
         w = (torch.zeros if args.zero else torch.randn)(args.n, Cin, 3, 3, device=dev) * 0.05
         b = torch.zeros(args.n, device=dev)
         cfg = ops.ConvCfg(1, ops.PAD_ZERO, 2)
-        d = ops._desc(x, None, w, cfg)
+        d = conv._desc(x, None, w, cfg)
         ohwi, ihwo = cfg.packed.get(w, dt, d.C1 + d.C2, d.Cout)
         y = torch.empty(B, d.Ho, d.Wo, d.Cout, device=dev, dtype=dt)
         st = torch.cuda.current_stream().cuda_stream
-        p = ops._p
+        p = core._p
         t = timeit(lambda: L.check(lib.uegan_conv2d_fwd(C.byref(d), p(x), None, p(ohwi), p(b), None, p(y), st)), args.iters)
         fl = 2.0 * B * H * H * args.n * 9 * Cin
         print("%6d %4d %10.4f %10.1f" % (Cin, B, t, fl / t / 1e9))

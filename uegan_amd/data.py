@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .ops import _p, lib
+from .ops.core import _p, lib
 
 _EXTS = ("png", "jpg", "jpeg", "JPG")
 PRECISION_BITS = 32 - 8 - 2           # Pillow, src/libImaging/Resample.c (8-bit channels)

@@ -1,5 +1,5 @@
 """Whole-network functions: the kernels of a FIXED network sequenced explicitly, forward and backward, inside one
-torch.autograd.Function each -- instead of one autograd node per layer (uegan_amd/ops.py), which costs an elementwise `add`
+torch.autograd.Function each -- instead of one autograd node per layer (uegan_amd/ops/), which costs an elementwise `add`
 kernel wherever an activation has two consumers, forces every repeated application of a network to be a separate pass, and
 cannot run a backward over part of a batch.
 
@@ -20,7 +20,8 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, _dt, _p, _stream, lib
+from .ops.conv import _desc, _dgrad, _sub_desc, refuse_stale_pack
+from .ops.core import ACT_NONE, ACT_RELU, _chk, _dt, _p, _sink_of, _stream, lib, workspace
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -164,7 +165,7 @@ class _VGGFidelityFn(torch.autograd.Function):
 def _dgrad_tap(d, dz, ihwo, t, ty, w, g, tmp, nb):
     """uegan_conv2d_dgrad_act_tap: dgrad(dz) * relu'(t) + the fidelity-loss gradient of tap t against ty (first nb images) in ONE launch --
     the data gradient, or None where the library declines (the caller then runs raw_conv_dgrad + uegan_percep_tap_bwd_acc)"""
-    d = ops._sub_desc(d, nb)
+    d = _sub_desc(d, nb)
     dx = torch.empty((d.B, d.H, d.W, d.C1), dtype=dz.dtype, device=dz.device)
     ok = C.c_int(0)
     L.check(lib().uegan_conv2d_dgrad_act_tap(C.byref(d), _p(dz), _p(ihwo), None, _p(dx), ACT_RELU, _p(t), _p(ty), float(w), _p(g), _p(tmp),
@@ -175,7 +176,7 @@ def _dgrad_tap(d, dz, ihwo, t, ty, w, g, tmp, nb):
 def _dgrad_unpool(d, dz, ihwo, yp, pidx, full_shape, nb):
     """uegan_conv2d_dgrad_unpool: the gradient of the 2x2 max-pool's INPUT (shape full_shape) from dgrad(dz) -- the gradient of its output -- in
     ONE launch, or None where the library declines (the caller then runs raw_conv_dgrad + uegan_maxpool2x2_bwd_idx)"""
-    d = ops._sub_desc(d, nb)
+    d = _sub_desc(d, nb)
     gx = torch.empty(full_shape, dtype=dz.dtype, device=dz.device)
     ok = C.c_int(0)
     L.check(lib().uegan_conv2d_dgrad_unpool(C.byref(d), _p(dz), _p(ihwo), None, _p(gx), ACT_RELU, _p(yp), _p(pidx), C.byref(ok), _stream()))
@@ -240,7 +241,7 @@ def _sn_rounds(trunks, n_rounds, do_iter, keep_uv):
         uh = torch.empty((n_rounds, rows), dtype=torch.float32, device=dev) if keep_uv else None
         vh = torch.empty((n_rounds, cols), dtype=torch.float32, device=dev) if keep_uv else None
         tmp = torch.empty((lib().uegan_specnorm_multi_workspace_floats(rows, cols),), dtype=torch.float32, device=dev)
-        ops._chk(w, m.weight_u, m.weight_v)
+        _chk(w, m.weight_u, m.weight_v)
         arr[i].w, arr[i].u, arr[i].v = _p(w), _p(m.weight_u), _p(m.weight_v)
         arr[i].sigma, arr[i].inv_sigma = _p(sig[0]), _p(sig[1])
         arr[i].u_hist, arr[i].v_hist, arr[i].tmp = _p(uh), _p(vh), _p(tmp)
@@ -287,7 +288,7 @@ class _DiscriminatorLossFn(torch.autograd.Function):
         recs, heads = [], []
         h = x
         for (trunk, head), (sig, inv, uh, vh) in zip(layers, sn):
-            desc = ops._desc(h, None, trunk.weight_orig, trunk.cfg)
+            desc = _desc(h, None, trunk.weight_orig, trunk.cfg)
             desc.scale_group = nb                                     # image b is scaled by 1/sigma of round b // nb
             ohwi, ihwo = trunk.cfg.packed.get(trunk.weight_orig, h.dtype, desc.C1, desc.Cout)
             y = torch.empty((desc.B, desc.Ho, desc.Wo, desc.Cout), dtype=h.dtype, device=h.device)
@@ -337,13 +338,13 @@ class _DiscriminatorLossFn(torch.autograd.Function):
             trunk, head = layers[li]
             d_in, desc, ihwo, y, hdesc, hihwo, tver, hver = recs[li]
             for cfgp, ver, saved in ((trunk.cfg.packed, tver, ihwo), (head.cfg.packed, hver, hihwo)):
-                if cfgp.ihwo is saved and cfgp.version != ver:
-                    # (the same refusal as ops._ConvFn.backward: `loss = discriminator_loss(...); optimizer.step(); loss.backward()`)
-                    raise RuntimeError("discriminator_loss backward: D's weights were updated by an optimizer step after this forward (the packed "
-                                       "copies saved for the data gradients have been rewritten in place); run backward() before step()")
+                # (the same refusal as ops.conv._ConvFn.backward: `loss = discriminator_loss(...); optimizer.step(); loss.backward()`)
+                refuse_stale_pack(cfgp, saved, ver,
+                                  "discriminator_loss backward: D's weights were updated by an optimizer step after this forward (the packed "
+                                  "copies saved for the data gradients have been rewritten in place); run backward() before step()")
             sig, inv, uh, vh = sn[li]
             dzp = sub(gmaps[li])                                      # pre-tanh gradient of this scale's prediction head
-            hd = ops._sub_desc(hdesc, nact)
+            hd = _sub_desc(hdesc, nact)
             ya = sub(y)
             # head -> trunk activation.  Where a kernel computes the gradient on the PADDED grid in one launch (head_dgrad_mfma_kernel) it is left
             # there: the activation backward below adds the mirror images while it reads it (`gh_pad` > 0) -- no fold pass, no folded copy
@@ -354,7 +355,7 @@ class _DiscriminatorLossFn(torch.autograd.Function):
             if train_d:
                 dw, _ = ops.raw_conv_wgrad(hd, ya, None, dzp, head.weight, None)
                 pgrads[id(head.weight)] = dw
-            td = ops._sub_desc(desc, nact)
+            td = _sub_desc(desc, nact)
             dz = torch.empty_like(ya)
             if train_d:
                 # dz = (gh + cur) * LeakyReLU'(y) / sigma_r per image group r, with the per-group projection coefficients of the spectral-norm
@@ -367,23 +368,21 @@ class _DiscriminatorLossFn(torch.autograd.Function):
                                                _p(inv[g0:]), _p(dz), _p(snws), nb * td.Ho * td.Wo, td.Ho, td.Wo, td.Cout, ngr, st)
                 if nbx <= 0:
                     L.check(nbx if nbx < 0 else -1)
-                scale_ptr, sg = None, 0
+                scale, sg = None, 0
             else:
                 # dz = (gh + cur) * LeakyReLU'(y): the two consumers of the trunk activation summed inside the activation backward
                 L.check(lib().uegan_act_bwd_p(_dt(gh), trunk.cfg.act, _p(gh), gh_pad, _p(cur), cur_pad, _p(ya), _p(dz), nact, td.Ho, td.Wo, td.Cout, st))
-                scale_ptr, sg = _p(inv[g0:]), nb                          # sub-batch image b' belongs to round g0 + b' // nb
+                scale, sg = inv[g0:], nb                              # sub-batch image b' belongs to round g0 + b' // nb
             if li > 0 or any(img_grad):
                 tds = L.ConvDesc.from_buffer_copy(td)
                 tds.scale_group = sg
                 # ... and the trunk conv's own data gradient: on the padded grid too where conv_flat_kernel takes the layer (d3 - d5), for the
                 # activation backward of the scale below; the gradient w.r.t. the images (li == 0) is wanted folded
-                cur, cur_pad = _dgrad_padded(tds, dz, ihwo, None, scale_ptr) if li > 0 else (None, 0)
+                cur, cur_pad = _dgrad_padded(tds, dz, ihwo, None, _p(scale)) if li > 0 else (None, 0)
                 if cur is None:
                     cur_pad = 0
                     cur = torch.empty((nact, td.H, td.W, td.C1), dtype=dz.dtype, device=dz.device)
-                    dwsb = lib().uegan_conv2d_dgrad_workspace_bytes(C.byref(tds))
-                    dws = torch.empty((dwsb + 3) // 4, dtype=torch.float32, device=dz.device) if dwsb else None
-                    L.check(lib().uegan_conv2d_dgrad_ws(C.byref(tds), _p(dz), _p(ihwo), scale_ptr, _p(cur), None, _p(dws), dwsb, st))
+                    _dgrad(tds, dz, ihwo, scale, cur, None)
             else:
                 cur, cur_pad = None, 0
             if train_d:
@@ -391,7 +390,7 @@ class _DiscriminatorLossFn(torch.autograd.Function):
                 # db (+)= sum dz_raw.  Straight into the optimizer bucket when there is one.
                 wd = w.detach()
                 rows, cols = wd.shape[0], wd[0].numel()
-                wsink, bsink = ops._sink_of(w), ops._sink_of(bias)
+                wsink, bsink = _sink_of(w), _sink_of(bias)
                 dw_acc = wsink.view if wsink is not None else torch.empty_like(wd)
                 db_acc = bsink.view if bsink is not None else torch.empty_like(bias.detach())
                 w_live = wsink is not None and wsink.dirty         # the bucket already holds a gradient of this step
@@ -399,7 +398,7 @@ class _DiscriminatorLossFn(torch.autograd.Function):
                 gd = L.ConvDesc.from_buffer_copy(td)
                 gd.scale_group = 0
                 wsb = lib().uegan_conv2d_wgrad_workspace_bytes(C.byref(gd))
-                ws = torch.empty((max(wsb, 4) + 3) // 4, dtype=torch.float32, device=wd.device)
+                ws = workspace(wsb, wd.device, least=4)
                 L.check(lib().uegan_conv2d_wgrad_acc(C.byref(gd), _p(sub(d_in)), None, _p(dz), None, _p(dw_acc), None, _p(ws), wsb, 1 if w_live else 0, st))
                 L.check(lib().uegan_sn_grad_finish(_p(dw_acc), _p(db_acc), _p(snws), nbx, ngr, _p(uh[g0:]), _p(vh[g0:]), rows, cols, td.Cout,
                                                    1 if b_live else 0, st))

@@ -37,6 +37,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .ops.core import _sink_of
 from . import variants
 
 
@@ -212,7 +213,7 @@ class _TouchParams(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, *params):
         ctx.meta = [(p.shape, p.dtype, p.device) for p in params]
-        ctx.sinks = [ops._sink_of(p) for p in params]
+        ctx.sinks = [_sink_of(p) for p in params]
         ctx.sunk = [sk is not None for sk in ctx.sinks]
         return y.view_as(y)
 
@@ -480,7 +481,7 @@ class Generator(_InvalidatingModule):
         X = ops.ConvExtras
         pre, at = (tile.moments, tile.at) if tile is not None else ((None,) * 5, lambda k: None)      # tile: see forward
         # encoder activations with several consumers (next encoder stage, attention module, final modulation) come back as one
-        # alias per consumer: their gradients meet inside the producing conv's activation-backward kernel (ops._ConvFn)
+        # alias per consumer: their gradients meet inside the producing conv's activation-backward kernel (ops.conv._ConvFn)
         ex1 = X(pair_w=True, dup_cin=True, want_lo=True) if P else None
         # the full-resolution attention modules ga1 / ga2 in the plain 16-bit modes: (encoder activation, module) is one graph node whose backward is one
         # streaming kernel (ops.gam_hub: InstanceNorm backward, both 1x1 gradients and the encoder's activation backward) where the library offers it

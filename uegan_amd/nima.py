@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from . import data, ops
+from . import data
+from .ops import core
 from .models import _InvalidatingModule
 
 INPUT_SIZE = 224          # CenterCrop(224); the trunk's five stride-2 stages leave the 7x7 map AvgPool2d(7) expects
@@ -123,7 +124,7 @@ class NIMA(_InvalidatingModule):
         return out
 
     def _plan(self):
-        key = (ops._weight_epoch[0], self.head[2].weight.device)
+        key = (core._weight_epoch[0], self.head[2].weight.device)
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         feats = self.base_model[0]
@@ -151,7 +152,7 @@ class NIMA(_InvalidatingModule):
         if self.training:
             raise RuntimeError("NIMA runs in eval mode only (BatchNorm with batch statistics is not built): call model.eval()")
         layers, fw, fb = self._plan()
-        lib, st, dev = ops.lib(), ops._stream(), x.device
+        lib, st, dev = core.lib(), core._stream(), x.device
         H = W = INPUT_SIZE
         cur, block_in = x, None
         for kind, w, scale, shift, lo, hi, stride, cout, residual, idx in layers:
@@ -194,7 +195,7 @@ class NIMA(_InvalidatingModule):
         if x.shape[2] != INPUT_SIZE or x.shape[3] != INPUT_SIZE:
             raise ValueError("NIMA expects %dx%d inputs (prepare_image makes them), got %dx%d" % (INPUT_SIZE, INPUT_SIZE, x.shape[2], x.shape[3]))
         x = x.detach().contiguous()
-        ops._chk(x)
+        core._chk(x)
         hw = INPUT_SIZE * INPUT_SIZE
         return self._run(x, (3 * hw, hw, INPUT_SIZE, 1), x.shape[0], taps)
 
@@ -234,7 +235,7 @@ def _prepare(images_u8, cpad):
     if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
         raise TypeError("prepare_image expects uint8 [B, h, w, 3] images (tester.to_uint8_image)")
     px = images_u8.contiguous()
-    ops._chk(px)
+    core._chk(px)
     B, h, w, _ = px.shape
     oh, ow = resized_size(h, w)
     if oh < INPUT_SIZE or ow < INPUT_SIZE:
@@ -245,8 +246,8 @@ def _prepare(images_u8, cpad):
     tmp = torch.empty((B, h, INPUT_SIZE, 3), dtype=torch.uint8, device=dev)
     shape = (B, 3, INPUT_SIZE, INPUT_SIZE) if cpad == 0 else (B, INPUT_SIZE, INPUT_SIZE, cpad)
     out = torch.empty(shape, dtype=torch.float32, device=dev)
-    L.check(ops.lib().uegan_nima_prepare(px.data_ptr(), B, h, w, INPUT_SIZE, INPUT_SIZE, htab.data_ptr(), hk, vtab.data_ptr(), vk, tmp.data_ptr(),
-                                         out.data_ptr(), cpad, ops._stream()))
+    L.check(core.lib().uegan_nima_prepare(px.data_ptr(), B, h, w, INPUT_SIZE, INPUT_SIZE, htab.data_ptr(), hk, vtab.data_ptr(), vk, tmp.data_ptr(),
+                                         out.data_ptr(), cpad, core._stream()))
     return out
 
 

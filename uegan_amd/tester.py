@@ -15,8 +15,8 @@
                                       border crop both scripts apply (:24,56), computed by libuegan_hip.so kernels
     mean_metric(values)               the TRUE mean; the reference's directory averages divide by N-1 (CalcPSNR.py:77, CalcSSIM.py:75)
     write_pngs(paths, images_u8)      the 8-bit images as PNG files, by the encoder set_png_encoder selects: "pillow" (the default: Image.save on the
-                                      host) or "device" (ops.png_encode: filter, deflate and CRCs in libuegan_hip.so, the host only writes)
-    write_images(paths, images_u8)    ... by the format set_image_format selects: "png" (write_pngs, the default) or "jpeg" (ops.jpeg_encode: baseline
+                                      host) or "device" (codecs.png_encode: filter, deflate and CRCs in libuegan_hip.so, the host only writes)
+    write_images(paths, images_u8)    ... by the format set_image_format selects: "png" (write_pngs, the default) or "jpeg" (codecs.jpeg_encode: baseline
                                       JPEG on the device, files named .jpg; set_image_format(optimize=True): with the image's own Huffman
                                       tables); returns the paths written
     run_test(G, loader, ...)          the loop of Tester.test (tester.py:40-105): enhance every batch of a test loader, write the
@@ -28,7 +28,8 @@ import math
 import torch
 
 from . import _lib as L
-from . import data, ops
+from . import codecs, data, ops
+from .ops.core import _chk, _p, _ptr_table, _stream, lib
 
 CROP_BORDER = 4          # CalcPSNR.py:24 / CalcSSIM.py:24
 
@@ -90,8 +91,8 @@ def to_uint8_image(x, window=None):
         raise TypeError("to_uint8_image expects a float32 [B,C,H,W] tensor")
     B, C, H, W = x.shape
     y = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
-    ops._chk(x, y)
-    L.check(ops.lib().uegan_quantize_u8(x.data_ptr(), y.data_ptr(), B, C, H, W, ops._stream()))
+    _chk(x, y)
+    L.check(lib().uegan_quantize_u8(x.data_ptr(), y.data_ptr(), B, C, H, W, _stream()))
     return y
 
 
@@ -123,11 +124,11 @@ def montage_u8(*images, window=None):
         if not (1 <= H <= Hs and 1 <= W <= Ws):
             raise ValueError("montage_u8: the %d x %d window does not fit the %d x %d images" % (H, W, Hs, Ws))
     y = torch.empty((B, H, n * W, C), dtype=torch.uint8, device=xs[0].device)
-    ops._chk(y, *xs)
+    _chk(y, *xs)
     if window is not None:
-        L.check(ops.lib().uegan_montage_crop_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, Hs, Ws, H, W, ops._stream()))
+        L.check(lib().uegan_montage_crop_u8(_ptr_table(xs), n, y.data_ptr(), B, C, Hs, Ws, H, W, _stream()))
     else:
-        L.check(ops.lib().uegan_montage_u8(ops._ptr_table(xs), n, y.data_ptr(), B, C, H, W, ops._stream()))
+        L.check(lib().uegan_montage_u8(_ptr_table(xs), n, y.data_ptr(), B, C, H, W, _stream()))
     return y
 
 
@@ -156,8 +157,8 @@ def montage_place_u8(dst, images, src_window, dst_origin, panel=None):
     if not (dy >= 0 and dx >= 0 and panel >= w and dy + h <= Hd and dx + (n - 1) * panel + w <= Wd):
         raise ValueError("montage_place_u8: %d panels of %d x %d (pitch %d) at (%d, %d) do not fit the %d x %d destination" % (n, h, w, panel, dy, dx, Hd, Wd))
     xs = [x.detach().contiguous() for x in images]
-    ops._chk(dst, *xs)
-    L.check(ops.lib().uegan_montage_place_u8(ops._ptr_table(xs), n, dst.data_ptr(), B, C, Hs, Ws, sy, sx, h, w, Hd, Wd, dy, dx, panel, ops._stream()))
+    _chk(dst, *xs)
+    L.check(lib().uegan_montage_place_u8(_ptr_table(xs), n, dst.data_ptr(), B, C, Hs, Ws, sy, sx, h, w, Hd, Wd, dy, dx, panel, _stream()))
     return dst
 
 
@@ -265,7 +266,7 @@ _png_encoder = "pillow"
 
 
 def set_png_encoder(name):
-    """who encodes the PNG files write_pngs writes: "pillow" (the default; files as before) or "device" (ops.png_encode: same pixels, another
+    """who encodes the PNG files write_pngs writes: "pillow" (the default; files as before) or "device" (codecs.png_encode: same pixels, another
     deflate stream).  Anything else: ValueError."""
     global _png_encoder
     if name not in PNG_ENCODERS:
@@ -284,7 +285,7 @@ def write_pngs(paths, images_u8):
     if len(paths) != images_u8.shape[0]:
         raise ValueError("write_pngs: %d paths for %d images" % (len(paths), images_u8.shape[0]))
     if _png_encoder == "device":
-        for path, blob in zip(paths, ops.png_encode(images_u8.contiguous())):
+        for path, blob in zip(paths, codecs.png_encode(images_u8.contiguous())):
             with open(path, "wb") as f:
                 f.write(blob)
         return
@@ -300,7 +301,7 @@ _jpeg_optimize = False
 
 
 def set_image_format(name, quality=95, subsampling="4:4:4", optimize=False):
-    """the container write_images writes: "png" (the default: write_pngs, every file name and byte as before) or "jpeg" (ops.jpeg_encode with this
+    """the container write_images writes: "png" (the default: write_pngs, every file name and byte as before) or "jpeg" (codecs.jpeg_encode with this
     quality, 1..100, and subsampling, "4:4:4" or "4:2:0": baseline JPEG files named .jpg, always encoded on the device -- there is no Pillow arm,
     and the PNG encoder selection does not matter to it).  optimize (a bool; "jpeg" only): every file carries its own Huffman tables, built on the
     device from its symbol counts, instead of the standard ones: the same pixels in a smaller file.  Anything else: ValueError, and the selection
@@ -310,8 +311,8 @@ def set_image_format(name, quality=95, subsampling="4:4:4", optimize=False):
         raise ValueError("unknown image format %r (one of %s)" % (name, ", ".join(IMAGE_FORMATS)))
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
         raise ValueError("JPEG quality %r is not an integer in [1, 100]" % (quality,))
-    if subsampling not in ops.JPEG_SUBSAMPLINGS:
-        raise ValueError("JPEG subsampling %r is not one of %s" % (subsampling, ", ".join(ops.JPEG_SUBSAMPLINGS)))
+    if subsampling not in codecs.JPEG_SUBSAMPLINGS:
+        raise ValueError("JPEG subsampling %r is not one of %s" % (subsampling, ", ".join(codecs.JPEG_SUBSAMPLINGS)))
     if not isinstance(optimize, bool):
         raise ValueError("JPEG optimize %r is not a bool" % (optimize,))
     if optimize and name != "jpeg":
@@ -347,7 +348,7 @@ def write_images(paths, images_u8):
     if len(paths) != images_u8.shape[0]:
         raise ValueError("write_images: %d paths for %d images" % (len(paths), images_u8.shape[0]))
     written = [image_path(p) for p in paths]
-    for path, blob in zip(written, ops.jpeg_encode(images_u8.contiguous(), quality, subsampling, optimize=_jpeg_optimize)):
+    for path, blob in zip(written, codecs.jpeg_encode(images_u8.contiguous(), quality, subsampling, optimize=_jpeg_optimize)):
         with open(path, "wb") as f:
             f.write(blob)
     return written
@@ -366,8 +367,8 @@ def _metrics(img1, img2, crop_border, want_sq, want_ssim):
     B, H, W, C = a.shape
     sq = torch.empty((B,), dtype=torch.float64, device=a.device) if want_sq else None
     ss = torch.empty((B,), dtype=torch.float64, device=a.device) if want_ssim else None
-    ops._chk(a, b)
-    L.check(ops.lib().uegan_image_metrics_u8(a.data_ptr(), b.data_ptr(), ops._p(sq), ops._p(ss), B, H, W, C, crop_border, ops._stream()))
+    _chk(a, b)
+    L.check(lib().uegan_image_metrics_u8(a.data_ptr(), b.data_ptr(), _p(sq), _p(ss), B, H, W, C, crop_border, _stream()))
     h, w = H - 2 * crop_border, W - 2 * crop_border
     return sq, ss, h * w * C, (h - 6) * (w - 6) * C
 

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .ops import _chk, _dt, _p, _ptr_table, _stream, lib
+from .ops.core import _chk, _dt, _p, _ptr_table, _stream, lib
 
 ACT_SIGMOID, ACT_SWISH, ACT_SELU = 4, 5, 6
 ACT_CODES = {"LeakyReLU": ops.ACT_LRELU, "ReLU": ops.ACT_RELU, "Swish": ACT_SWISH, "SELU": ACT_SELU, "none": ops.ACT_NONE}
