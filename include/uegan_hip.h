@@ -444,6 +444,48 @@ int uegan_jpeg_histogram(const int16_t* coeffs, int B, int H, int W, int subsamp
 int uegan_jpeg_build_tables(const uint64_t* hist, int n, uint8_t* dht, uint32_t* codes, uegan_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Baseline JPEG files READ on the device (jpeg_decode.hip): pixels equal to libjpeg's default decode (Pillow's) byte for byte.  The host parses
+ * the header up to SOS into the descriptor below (uegan_amd/codecs.py: jpeg_info) and never touches the entropy-coded bytes.
+ * Accepted: SOF0, 8-bit samples and tables, one interleaved scan over all components (Ss, Se, Ah/Al = 0, 63, 0), any DHT, with or without DRI;
+ * one component, or three with luma 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0) that libjpeg would read as YCbCr.
+ * Stages: (1) unstuff -- FF 00 -> FF, FF FF.. is fill, FF D0..D7 ends a restart interval (their count and k mod 8 sequence are checked against
+ * the geometry), the first other marker ends the scan; (2) entropy decoding -- an interval is cut into sub-sequences of subseq_bits bits (0: one
+ * per interval; otherwise a multiple of 32 in [128, 2^20], 1024 is the usual value), every sub-sequence is decoded from a blind start and then
+ * again from its predecessor's exit state until a round changes nothing (a fixed point that equals the serial decode), a last pass writes int16
+ * coefficients; (3) dequantisation, libjpeg's integer "islow" inverse DCT, "fancy" chroma up-sampling, fixed-point YCbCr -> RGB.
+ * UNLIKE the other entry points these SYNCHRONISE `stream`: the host reads 256 control bytes after round 0, after every launch of up to 8
+ * rounds, and at the end.  No kernel waits on another block; max_rounds (>= 1) bounds the rounds, a file that needs more returns
+ * UEGAN_E_JPEG_DESYNC.  A stream whose markers, codes or block counts contradict the header returns UEGAN_E_JPEG_STREAM; the outputs then hold
+ * nothing of use, and nothing outside them has been written.
+ * ------------------------------------------------------------------------------------------------- */
+enum { UEGAN_E_JPEG_DESYNC = -4,      /* "not synchronised": the sub-sequences did not reach the fixed point within max_rounds */
+       UEGAN_E_JPEG_STREAM = -5 };    /* the entropy-coded data contradict the header */
+typedef struct uegan_jpeg_table {
+  uint8_t counts[16];                 /* codes of length 1..16 */
+  uint8_t symbols[256];               /* in code order, zero-filled */
+} uegan_jpeg_table;
+typedef struct uegan_jpeg_desc {
+  int32_t H, W, ncomp;                /* ncomp 1 (grayscale; h, v are ignored) or 3 (Y, Cb, Cr) */
+  int32_t restart_interval;           /* MCUs, 0: none */
+  int32_t h[4], v[4];                 /* sampling factors per component */
+  int32_t tq[4], td[4], ta[4];        /* quantisation, DC and AC table of each component */
+  int64_t scan_offset, scan_length;   /* the bytes behind SOS: first byte in the file, how many to look at (up to the file's end) */
+  uint8_t quant[4][64];               /* zigzag order, as DQT holds them */
+  uegan_jpeg_table dc[4], ac[4];
+} uegan_jpeg_desc;
+/* workspace bytes for one file (0: the descriptor or subseq_bits is refused) */
+size_t uegan_jpeg_decode_workspace_bytes(const uegan_jpeg_desc* desc, int subseq_bits);
+/* file: DEVICE, the whole file (any alignment) -> pixels: DEVICE uint8 [H][W][3], 16-byte aligned.  desc: HOST.  stats: HOST int32 [4] or NULL:
+ * rounds used (1: round 0 alone), sub-sequences, restart intervals, bytes of the unstuffed stream.  stage_ms: HOST float [4] or NULL: HIP-event
+ * times of unstuff / round 0 and the rounds / write pass and DC sums / pixels.  workspace: DEVICE, 16-byte aligned. */
+int uegan_jpeg_decode(const uint8_t* file, const uegan_jpeg_desc* desc, int subseq_bits, int max_rounds, uint8_t* pixels, int32_t* stats, float* stage_ms,
+                      void* workspace, uegan_stream_t stream);
+/* Stages 1 and 2 alone -> coeffs: DEVICE int16 [component][block row][block col][64], zigzag order, every plane covering whole MCUs (the layout
+ * of uegan_jpeg_coeffs for one image), 16-byte aligned. */
+int uegan_jpeg_decode_coeffs(const uint8_t* file, const uegan_jpeg_desc* desc, int subseq_bits, int max_rounds, int16_t* coeffs, int32_t* stats, void* workspace,
+                             uegan_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Input pipeline on the device (data_loader.py:74-82 train transform, :95-100 test transform, :126 H2D)
  * ------------------------------------------------------------------------------------------------- */
 /* pixels: B (<= 64) crop windows of decoded 8-bit RGB images, DEVICE uint8 [B][in_h][in_w][3] (the RandomCrop of

@@ -53,6 +53,17 @@ class AdamTensor(C.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", c_i64)]
 
 
+class JpegTable(C.Structure):
+    _fields_ = [("counts", C.c_uint8 * 16), ("symbols", C.c_uint8 * 256)]
+
+
+class JpegDesc(C.Structure):
+    """uegan_jpeg_desc: what uegan_jpeg_decode needs of a file's header (codecs.jpeg_info fills it)"""
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("ncomp", C.c_int32), ("restart_interval", C.c_int32), ("h", C.c_int32 * 4), ("v", C.c_int32 * 4),
+                ("tq", C.c_int32 * 4), ("td", C.c_int32 * 4), ("ta", C.c_int32 * 4), ("scan_offset", c_i64), ("scan_length", c_i64),
+                ("quant", (C.c_uint8 * 64) * 4), ("dc", JpegTable * 4), ("ac", JpegTable * 4)]
+
+
 # name -> (restype, argtypes).  Every symbol include/uegan_hip.h declares must be listed here
 # (tests/test_abi.py cross-checks the header against this table and against the built library).
 SIGNATURES = {
@@ -175,6 +186,9 @@ SIGNATURES = {
     "uegan_jpeg_workspace_bytes_ex": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "uegan_jpeg_histogram": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_jpeg_build_tables": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
+    "uegan_jpeg_decode_workspace_bytes": (c_sz, [C.POINTER(JpegDesc), c_int]),
+    "uegan_jpeg_decode": (c_int, [c_vp, C.POINTER(JpegDesc), c_int, c_int, c_vp, C.POINTER(C.c_int32), C.POINTER(c_f32), c_vp, c_vp]),
+    "uegan_jpeg_decode_coeffs": (c_int, [c_vp, C.POINTER(JpegDesc), c_int, c_int, c_vp, C.POINTER(C.c_int32), c_vp, c_vp]),
     "uegan_native_input":(c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),

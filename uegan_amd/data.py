@@ -352,6 +352,39 @@ def _decode_whole(path, dst):
         dst[...] = np.asarray(im.convert("RGB"))
 
 
+# who decodes the input files: "host" (Pillow in the workers, the pixels copied up) or "device" (the workers read the files' bytes and parse their
+# headers; codecs.jpeg_decode_into decodes baseline JPEG files on the loader's side stream; any other file takes the Pillow route, one by one)
+INPUT_DECODERS = ("host", "device")
+_input_decoder = "host"
+
+
+def set_input_decoder(name):
+    """the decoder of the loaders created from now on without a `decode` of their own: "host" (default) or "device"; returns the previous one"""
+    global _input_decoder
+    if name not in INPUT_DECODERS:
+        raise ValueError("unknown input decoder %r (one of %s)" % (name, ", ".join(INPUT_DECODERS)))
+    prev, _input_decoder = _input_decoder, name
+    return prev
+
+
+def get_input_decoder():
+    return _input_decoder
+
+
+def _read_file(path, size, dst, h, w):
+    """worker of the device decoder: the file's bytes into the slot, its header parsed -> codecs.JpegInfo, or None for a file the device decoder
+    declines (no JPEG, not baseline, ...: codecs.jpeg_info) or that changed since it was listed"""
+    from . import codecs
+    with open(path, "rb") as f:
+        if f.readinto(dst) != size or f.read(1):
+            return None
+    try:
+        info = codecs.jpeg_info(memoryview(dst))
+    except codecs.JpegUnsupported:
+        return None
+    return info if (info.height, info.width) == (h, w) else None
+
+
 _SIZES = {}
 
 
@@ -375,14 +408,23 @@ class DeviceLoader:
                  file as a uint8 [1,h,w,3] device tensor (tester.enhance_native / run_test take them from there)"""
 
     def __init__(self, dataset, batch_size, img_size=512, resize_size=256, train=True, shuffle=True, drop_last=True, num_workers=8,
-                 device=None, prefetch=2, generator=None, shard=None, shard_seed=0, workers="thread"):
+                 device=None, prefetch=2, generator=None, shard=None, shard_seed=0, workers="thread", decode=None):
         """shard = (rank, world_size): this process iterates samples rank, rank + world, ... of the (shuffled) order -- one
         loader per GPU process.  The permutation of epoch e is then drawn from its own generator seeded
         shard_seed + e (the same on every rank, like DistributedSampler.set_epoch); crops and flips stay per-rank draws.
         workers: "thread" (decode in threads of this process: enough up to ~600 img/s, then the interpreter lock shared with the
         training loop caps it) or "process" (spawned decode processes writing into shared-memory segments that are page-locked
         for the H2D copy -- what DataLoader(num_workers=N) does, minus the transform and the pickling of tensors; as with any
-        spawned pool, the launching script needs its `if __name__ == "__main__":` guard)."""
+        spawned pool, the launching script needs its `if __name__ == "__main__":` guard).
+        decode: "host" (Pillow in the workers), "device" (baseline JPEG files are decoded on the device from their bytes, bit-exact with Pillow, so the
+        tensors are the same; every other file takes the Pillow route and is counted in `fallbacks`, per pass, and `fallbacks_total`), or None: what
+        set_input_decoder() chose.  "device" reads the files in threads."""
+        self.decode = _input_decoder if decode is None else decode
+        if self.decode not in INPUT_DECODERS:
+            raise ValueError("unknown input decoder %r (one of %s)" % (self.decode, ", ".join(INPUT_DECODERS)))
+        if self.decode == "device" and workers == "process":
+            raise ValueError("decode='device' reads the files in threads: workers must be 'thread'")
+        self.fallbacks = self.fallbacks_total = 0
         self.dataset, self.batch_size, self.img_size, self.resize_size = dataset, batch_size, img_size, resize_size
         self.train, self.shuffle, self.drop_last = train, shuffle, drop_last
         self.native = not train and img_size == 0
@@ -449,6 +491,56 @@ class DeviceLoader:
 
     # -- stage 1: host decode into the pinned buffer (threads) -------------------------------------------------------
     def _submit(self, slot, indices):
+        if self.decode == "device":
+            return self._submit_files(slot, indices)
+        return self._submit_pixels(slot, indices)
+
+    def _draw(self, slot, indices, align):
+        """the wait for the slot's earlier use, the items and the plan of a batch: per file (path, top, left, h, w, flip bits, offset of its pixels)"""
+        for f in getattr(slot, "futures", None) or []:      # decodes left pending by an abandoned iterator still write into this slot
+            try:
+                f.result()
+            except Exception:
+                pass
+        slot.futures = []
+        if slot.copied is not None:
+            slot.copied.synchronize()            # the previous H2D copy out of this pinned buffer has finished
+            slot.copied = None
+        items = [self.dataset[i] for i in indices]
+        plan, off = [], 0
+        for a, b, name in items:
+            for path in (a, b):
+                h, w = _image_size(path)
+                if align:
+                    off = (off + 15) // 16 * 16
+                if self.train:
+                    top, left, bits = draw_train_params(h, w, self.img_size, self.generator)
+                    plan.append((path, top, left, self.img_size, self.img_size, bits, off))
+                    off += self.img_size * self.img_size * 3
+                else:
+                    plan.append((path, 0, 0, h, w, 0, off))
+                    off += h * w * 3
+        return items, plan, off
+
+    def _submit_files(self, slot, indices):
+        """decode="device": the slot holds the pixel regions of _submit_pixels (16-byte aligned; a file of the Pillow route is decoded into its own)
+        and, behind them, every file's bytes; a worker reads the file and parses its header"""
+        items, plan, off = self._draw(slot, indices, True)
+        pixel_bytes = off = (off + 15) // 16 * 16
+        files = []
+        for path, *_ in plan:
+            size = os.path.getsize(path)
+            files.append((off, size))
+            off += (size + 15) // 16 * 16
+        slot.ensure(off, self.device, pinned=not self.emulated, shared=False, mirror=not self.native)
+        host = slot.host.numpy()
+        for (path, _, _, _, _, _, _), (fo, size) in zip(plan, files):
+            h, w = _image_size(path)
+            slot.futures.append(self.pool.submit(_read_file, path, size, host[fo:fo + size], h, w))
+        slot.items, slot.plan, slot.nbytes, slot.out = items, plan, off, None
+        slot.files, slot.pixel_bytes = files, pixel_bytes
+
+    def _submit_pixels(self, slot, indices):
         for f in getattr(slot, "futures", None) or []:      # decodes left pending by an abandoned iterator still write into this slot
             try:
                 f.result()
@@ -487,6 +579,44 @@ class DeviceLoader:
         slot.items, slot.plan, slot.nbytes, slot.out = items, plan, off, None
 
     # -- stage 2: one H2D copy + the transform kernels, on the side stream -------------------------------------------
+    def _upload_files(self, slot, stream_handle):
+        """decode="device": the files' bytes go up in one copy and are decoded on this stream into the pixel regions the transforms read (train: the
+        whole image into a buffer of its own, the crop window copied out of it).  A file without a header the device takes, or whose decode returns
+        a status, is decoded by Pillow here and its pixels copied up alone.  -> the device buffer that holds the pixel regions"""
+        from . import codecs
+        infos = [f.result() for f in slot.futures]
+        lo, hi = slot.pixel_bytes, slot.nbytes
+        if self.native:      # (as in _upload: the batch is a buffer of its own)
+            pix = torch.empty((slot.pixel_bytes,), dtype=torch.uint8, device=self.device)
+            fdev, base = torch.empty((hi - lo,), dtype=torch.uint8, device=self.device), lo
+        else:
+            pix, fdev, base = slot.dev, slot.dev, 0
+        fdev[lo - base:hi - base].copy_(slot.host[lo:hi], non_blocking=True)
+        host = slot.host.numpy()
+        for info, (path, top, left, h, w, _, o), (fo, size) in zip(infos, slot.plan, slot.files):
+            region = pix[o:o + h * w * 3]
+            if info is not None:
+                try:
+                    blob = fdev[fo - base:fo - base + size]
+                    if self.train:
+                        whole = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=self.device)
+                        codecs.jpeg_decode_into(info, blob, whole, stream=stream_handle)
+                        region.view(h, w, 3).copy_(whole[top:top + h, left:left + w])
+                    else:
+                        codecs.jpeg_decode_into(info, blob, region, stream=stream_handle)
+                    continue
+                except codecs.JpegDecodeError:
+                    pass
+            self.fallbacks += 1
+            self.fallbacks_total += 1
+            dst = host[o:o + h * w * 3].reshape(h, w, 3)
+            if self.train:
+                _decode_window(path, top, left, h, w, dst)
+            else:
+                _decode_whole(path, dst)
+            region.copy_(slot.host[o:o + h * w * 3], non_blocking=True)
+        return pix
+
     def _upload(self, slot):
         for f in slot.futures:
             f.result()                           # (re-raises decode errors here)
@@ -494,6 +624,22 @@ class DeviceLoader:
         S = self.resize_size if self.train else self.img_size
 
         def run(stream_handle):
+            if self.decode == "device":
+                pix = self._upload_files(slot, stream_handle)
+                if self.native:
+                    return pix
+                out = torch.empty((2 * B, 3, S, S), dtype=torch.float32, device=self.device)
+                if self.train:
+                    c = self.img_size
+                    if all(p_[6] == i * c * c * 3 for i, p_ in enumerate(slot.plan)):      # (the 16-byte alignment left no gaps: one call, as "host")
+                        input_transform(pix[:2 * B * c * c * 3].view(2 * B, c, c, 3), S, [p_[5] for p_ in slot.plan], out=out, stream=stream_handle)
+                    else:
+                        for i, p_ in enumerate(slot.plan):
+                            input_transform(pix[p_[6]:p_[6] + c * c * 3].view(1, c, c, 3), S, [p_[5]], out=out[i:i + 1], stream=stream_handle)
+                else:
+                    for i, (path, _, _, h, w, _, o) in enumerate(slot.plan):
+                        input_transform(pix[o:o + h * w * 3].view(1, h, w, 3), S, None, out=out[i:i + 1], stream=stream_handle)
+                return out
             if self.native:      # the batch IS the copied bytes: a buffer of its own (slot.dev is overwritten by the slot's next batch)
                 dev = torch.empty((slot.nbytes,), dtype=torch.uint8, device=self.device)
                 dev.copy_(slot.host[:slot.nbytes], non_blocking=True)
@@ -519,6 +665,7 @@ class DeviceLoader:
             slot.ready = slot.copied
 
     def __iter__(self):
+        self.fallbacks = 0
         order = self._order()
         bs = self.batch_size
         batches = [order[i:i + bs] for i in range(0, len(order), bs)]
@@ -560,17 +707,17 @@ class DeviceLoader:
 
 
 def get_train_loader(root, img_size=512, resize_size=256, batch_size=8, shuffle=True, num_workers=8, drop_last=True, device=None, generator=None,
-                     shard=None, shard_seed=0, workers="thread"):
+                     shard=None, shard_seed=0, workers="thread", decode=None):
     """data_loader.py:72-90 with the transform on the device"""
     return DeviceLoader(ReferenceDataset(root), batch_size, img_size, resize_size, True, shuffle, drop_last, num_workers, device, generator=generator,
-                        shard=shard, shard_seed=shard_seed, workers=workers)
+                        shard=shard, shard_seed=shard_seed, workers=workers, decode=decode)
 
 
-def get_test_loader(root, img_size=512, batch_size=8, shuffle=False, num_workers=4, device=None, generator=None, workers="thread"):
+def get_test_loader(root, img_size=512, batch_size=8, shuffle=False, num_workers=4, device=None, generator=None, workers="thread", decode=None):
     """data_loader.py:93-110.  img_size=0: the native mode of DeviceLoader (NativeBatch: the decoded files as they are, for tester.run_test /
     tester.enhance_native to enhance at their own size)"""
     return DeviceLoader(ReferenceDataset(root), batch_size, img_size, img_size, False, shuffle, False, num_workers, device, generator=generator,
-                        workers=workers)
+                        workers=workers, decode=decode)
 
 
 class InputFetcher:

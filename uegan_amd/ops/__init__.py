@@ -20,7 +20,8 @@ place to watch or replace for "did anything reach the kernel library".
 from .. import _lib as L  # noqa: F401
 # (codecs imports .ops.core, so it can only be imported once this package has begun to: uegan_amd/__init__.py imports .ops before anything names codecs)
 from ..codecs import (JPEG_MAX_SIDE, JPEG_SUBSAMPLINGS, PNG_MAX_BAND, deflate_bands, jpeg_build_tables, jpeg_capacity,  # noqa: F401
-                      jpeg_coeffs, jpeg_encode, jpeg_histogram, jpeg_qtables, jpeg_sizes, png_encode)
+                      jpeg_coeffs, jpeg_encode, jpeg_histogram, jpeg_qtables, jpeg_sizes, png_encode,
+                      JpegDecodeError, JpegUnsupported, jpeg_decode, jpeg_decode_coeffs, jpeg_decode_into, jpeg_info)
 from .conv import (ConvCfg, ConvExtras, PackedWeight, PackTable, SNCall, StatsHolder, _ConvFn, _desc, _sub_desc, conv2d,  # noqa: F401
                    raw_conv_dgrad, raw_conv_fwd, raw_conv_wgrad, refuse_stale_pack, specnorm_sigma, split_k)
 from .core import (ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, IN_EPS, PAD_REFLECT, PAD_ZERO, SN_EPS, GradSink, _chk, _dt, _farr, _p,  # noqa: F401

@@ -301,6 +301,21 @@ def _apply_png_encoder():
     tester.set_png_encoder(name)
 
 
+INPUT_DECODER_ENV = "UEGAN_INPUT_DECODER"
+
+
+def _apply_input_decoder():
+    """UEGAN_INPUT_DECODER=host|device in the environment selects who decodes the input files of the run's loaders (data.set_input_decoder: "device"
+    decodes baseline JPEG files on the device, bit-exact with Pillow, and leaves every other file to Pillow); unset: the selection stays (default
+    "host").  Any other value is refused by name.  It is not a flag: the flag set is the reference's."""
+    name = os.environ.get(INPUT_DECODER_ENV)
+    if name is None:
+        return
+    if name not in data.INPUT_DECODERS:
+        raise ValueError("%s=%r: expected one of %s" % (INPUT_DECODER_ENV, name, ", ".join(data.INPUT_DECODERS)))
+    data.set_input_decoder(name)
+
+
 IMAGE_FORMAT_ENV = "UEGAN_IMAGE_FORMAT"
 JPEG_QUALITY_ENV = "UEGAN_JPEG_QUALITY"
 JPEG_OPTIMIZE_ENV = "UEGAN_JPEG_OPTIMIZE"
@@ -333,6 +348,7 @@ def _apply_image_format():
 def main(argv=None):
     _apply_png_encoder()
     _apply_image_format()
+    _apply_input_decoder()
     args = argv if hasattr(argv, "mode") else config.get_config(argv)
     if args.mode not in ("train", "test"):
         raise NotImplementedError("Mode [{}] is not found".format(args.mode))                                          # main.py:50
