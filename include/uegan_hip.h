@@ -497,6 +497,23 @@ int uegan_jpeg_decode_coeffs(const uint8_t* file, const uegan_jpeg_desc* desc, i
  * the layout InputFetcher hands to the trainer (:124-127).  tmp: DEVICE uint8 [B][in_h][out_w][3] scratch.  Bit-exact. */
 int uegan_input_transform(const uint8_t* pixels, int B, int in_h, int in_w, int out_h, int out_w, const int32_t* htab, int hk,
                           const int32_t* vtab, int vk, const int32_t* flips, uint8_t* tmp, float* out_nchw, uegan_stream_t stream);
+/* One crop window of an image that is RESIDENT in device memory (the dataset cache of uegan_amd/data.py): image is DEVICE uint8
+ * [height][pitch_px][3] of which the first `width` pixels of a row are the picture (pitch_px >= width: the image may be a view into a wider
+ * one; no alignment is asked of `image`), the window starts at row `top`, column `left`; flip_bits as the flips of uegan_input_transform. */
+typedef struct uegan_window {
+  const uint8_t* image;
+  int32_t pitch_px;
+  int32_t top, left;
+  int32_t flip_bits;
+  int32_t height, width;
+} uegan_window;
+/* uegan_input_transform with the crop done by the kernel: image b of the batch is the win_h x win_w window of windows[b] (HOST array of B <= 64
+ * descriptors; the images of one call may differ in size, pitch and base), read in place -- no copy of the window is made.  The arithmetic, the
+ * tables, tmp (DEVICE uint8 [B][win_h][out_w][3]) and out_nchw are those of uegan_input_transform, so the result is bit for bit the one that call
+ * gives for the contiguous copies of the same windows.  Every window is checked against its image before anything is launched:
+ * top, left >= 0, top + win_h <= height, left + win_w <= width, pitch_px >= width; one that fails returns UEGAN_E_INVALID and nothing is written. */
+int uegan_input_transform_windows(const uegan_window* windows, int B, int win_h, int win_w, int out_h, int out_w, const int32_t* htab, int hk,
+                                  const int32_t* vtab, int vk, uint8_t* tmp, float* out_nchw, uegan_stream_t stream);
 /* Native-size input: ToTensor + Normalize(0.5, 0.5) of B decoded images, DEVICE uint8 [B][h][w][3], with NO resize, extended by
  * reflection at the bottom and right to hp >= h rows and wp >= w columns (hp - h < h, wp - w < w, wp a multiple of 4, out_nchw 16-byte
  * aligned) in one pass: out_nchw fp32 [B][3][hp][wp], row y >= h = source row 2(h-1) - y, column x >= w = source column 2(w-1) - x --

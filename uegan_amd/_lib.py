@@ -64,6 +64,12 @@ class JpegDesc(C.Structure):
                 ("quant", (C.c_uint8 * 64) * 4), ("dc", JpegTable * 4), ("ac", JpegTable * 4)]
 
 
+class Window(C.Structure):
+    """uegan_window: one crop window of an image resident in device memory (uegan_input_transform_windows)"""
+    _fields_ = [("image", c_vp), ("pitch_px", C.c_int32), ("top", C.c_int32), ("left", C.c_int32), ("flip_bits", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32)]
+
+
 # name -> (restype, argtypes).  Every symbol include/uegan_hip.h declares must be listed here
 # (tests/test_abi.py cross-checks the header against this table and against the built library).
 SIGNATURES = {
@@ -191,6 +197,7 @@ SIGNATURES = {
     "uegan_jpeg_decode_coeffs": (c_int, [c_vp, C.POINTER(JpegDesc), c_int, c_int, c_vp, C.POINTER(C.c_int32), c_vp, c_vp]),
     "uegan_native_input":(c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "uegan_input_transform": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "uegan_input_transform_windows": (c_int, [C.POINTER(Window), c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
     "uegan_image_metrics_u8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "uegan_nima_prepare": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
     "uegan_nima_conv3x3_first": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f32, c_f32, c_vp]),

@@ -41,6 +41,37 @@ __global__ void resample_h_kernel(const uint8_t* pix, uint8_t* tmp, const int32_
   }
 }
 
+// pass 1 over windows of RESIDENT images (uegan_input_transform_windows): the same sums, the source addressed per image.  origin[b] points at the
+// window's first pixel (image + (top * pitch + left) * 3, computed and bounds-checked by the launcher), row y of the window lies y * pitch pixels
+// further.  The table goes by value like FlipTable (768 bytes of kernel arguments, no copy); tmp is written as resample_h_kernel writes it, so
+// pass 2 is resample_v_norm_kernel itself.  Byte loads only: a window's origin has no alignment.  One image per blockIdx.y: origin and pitch are
+// uniform in a block (scalar loads of the arguments), and an item's (y, xo) comes from one 32-bit division.
+struct WindowTable { const uint8_t* origin[INPUT_MAX_IMAGES]; int32_t pitch[INPUT_MAX_IMAGES]; };
+constexpr int WINDOWS_BLOCKS_PER_IMAGE = 512;      // grid cap of pass 1 per image: 512 x 256 threads are one per item at 512 -> 256; above, grid stride
+
+__global__ void resample_h_windows_kernel(WindowTable wt, uint8_t* tmp, const int32_t* tab, int K, int H, int OW) {
+  const int b = blockIdx.y;
+  const uint8_t* origin = wt.origin[b];
+  const size_t pitch = (size_t)wt.pitch[b];
+  uint8_t* dst = tmp + (size_t)b * H * OW * 3;
+  const uint32_t total = (uint32_t)H * (uint32_t)OW;                  // (the launcher checked that it fits)
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const uint32_t y = i / (uint32_t)OW, xo = i - y * (uint32_t)OW;
+    const int32_t* t = tab + (size_t)xo * (K + 2);
+    const int x0 = t[0], n = t[1];
+    const uint8_t* p = origin + (y * pitch + x0) * 3;
+    int s0 = 1 << (RESAMPLE_PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int k = 0; k < n; ++k) {
+      const int c = t[2 + k];
+      s0 += p[3 * k] * c; s1 += p[3 * k + 1] * c; s2 += p[3 * k + 2] * c;
+    }
+    uint8_t* q = dst + (size_t)i * 3;
+    q[0] = (uint8_t)clip8(s0 >> RESAMPLE_PRECISION_BITS);
+    q[1] = (uint8_t)clip8(s1 >> RESAMPLE_PRECISION_BITS);
+    q[2] = (uint8_t)clip8(s2 >> RESAMPLE_PRECISION_BITS);
+  }
+}
+
 __global__ void resample_v_norm_kernel(const uint8_t* tmp, float* out, const int32_t* tab, int K, FlipTable flips, int B, int H, int OH, int OW) {
   const size_t total = (size_t)B * OH * OW;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -195,6 +226,38 @@ extern "C" int uegan_input_transform(const uint8_t* pixels, int B, int in_h, int
   hipLaunchKernelGGL(resample_h_kernel, dim3(b1), dim3(256), 0, s, pixels, tmp, htab, hk, B, in_h, in_w, out_w);
   UEGAN_CHECK_LAUNCH();
   hipLaunchKernelGGL(resample_v_norm_kernel, dim3(b2), dim3(256), 0, s, (const uint8_t*)tmp, out_nchw, vtab, vk, ft, B, in_h, out_h, out_w);
+  UEGAN_CHECK_LAUNCH();
+  return UEGAN_OK;
+}
+
+extern "C" int uegan_input_transform_windows(const uegan_window* windows, int B, int win_h, int win_w, int out_h, int out_w, const int32_t* htab, int hk,
+                                             const int32_t* vtab, int vk, uint8_t* tmp, float* out_nchw, uegan_stream_t stream) {
+  UEGAN_CHECK_ARG(windows && htab && vtab && tmp && out_nchw, "input_transform_windows: null pointer");
+  UEGAN_CHECK_ARG(B >= 1 && B <= INPUT_MAX_IMAGES, "input_transform_windows takes 1..%d windows per call (got %d)", INPUT_MAX_IMAGES, B);
+  UEGAN_CHECK_ARG(win_h > 0 && win_w > 0 && out_h > 0 && out_w > 0 && hk >= 1 && vk >= 1, "input_transform_windows: bad geometry");
+  UEGAN_CHECK_ARG((int64_t)win_h * out_w < ((int64_t)1 << 31), "input_transform_windows: %d rows x %d output columns do not fit a 32-bit index", win_h, out_w);
+  WindowTable wt;
+  FlipTable ft;
+  for (int i = 0; i < INPUT_MAX_IMAGES; ++i) { wt.origin[i] = nullptr; wt.pitch[i] = 0; ft.bits[i] = 0; }
+  for (int i = 0; i < B; ++i) {      // every window inside its image, before anything is launched (64-bit sums: no wrap-around passes the test)
+    const uegan_window& w = windows[i];
+    UEGAN_CHECK_ARG(w.image, "input_transform_windows: window %d has no image", i);
+    UEGAN_CHECK_ARG(w.height >= 1 && w.width >= 1 && w.pitch_px >= w.width, "input_transform_windows: window %d: bad image (%d x %d, pitch %d pixels)", i,
+                    w.height, w.width, w.pitch_px);
+    UEGAN_CHECK_ARG(w.top >= 0 && w.left >= 0 && (int64_t)w.top + win_h <= w.height && (int64_t)w.left + win_w <= w.width,
+                    "input_transform_windows: window %d (%d x %d at row %d, column %d) leaves its %d x %d image", i, win_h, win_w, w.top, w.left, w.height,
+                    w.width);
+    wt.origin[i] = w.image + ((size_t)w.top * w.pitch_px + w.left) * 3;
+    wt.pitch[i] = w.pitch_px;
+    ft.bits[i] = w.flip_bits;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n1 = (size_t)win_h * out_w, n2 = (size_t)B * out_h * out_w;      // pass 1: items per image
+  const int b1 = (int)((n1 + 255) / 256 < (size_t)WINDOWS_BLOCKS_PER_IMAGE ? (n1 + 255) / 256 : (size_t)WINDOWS_BLOCKS_PER_IMAGE);
+  const int b2 = (int)((n2 + 255) / 256 < 16384 ? (n2 + 255) / 256 : 16384);
+  hipLaunchKernelGGL(resample_h_windows_kernel, dim3(b1, B), dim3(256), 0, s, wt, tmp, htab, hk, win_h, out_w);
+  UEGAN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(resample_v_norm_kernel, dim3(b2), dim3(256), 0, s, (const uint8_t*)tmp, out_nchw, vtab, vk, ft, B, win_h, out_h, out_w);
   UEGAN_CHECK_LAUNCH();
   return UEGAN_OK;
 }

@@ -10,6 +10,9 @@ only decodes files and copies raw bytes, and everything torchvision does per pix
   DataLoader(pin_memory=True) + InputFetcher (:85-90,       DeviceLoader: decode threads -> pinned ring -> side-stream H2D + transform,
       :113-133: `.to(device)` on the training stream)       `prefetch` batches ahead; the training stream only waits on an event
 
+  (nothing: every epoch decodes every file again)           cache="device" (opt-in): the decoded files stay in device memory from their first touch
+                                                            on (_ResidentStore) and uegan_input_transform_windows cuts the crops out of them in place
+
 Random draws follow torchvision's call order per image (RandomCrop.get_params: randint for the top row, randint for the left
 column -- none when the image already has the crop size; then one torch.rand(1) < 0.5 per flip), img_exp before img_raw as
 ReferenceDataset.__getitem__ transforms them (:63-65), and torch.randperm for the shuffle.  With DataLoader worker processes the
@@ -104,6 +107,41 @@ def input_transform(pixels, out_size, flips=None, out=None, stream=None):
         if flips is not None:
             fl = (L.C.c_int32 * nb)(*[int(f) for f in flips[b0:b0 + nb]])
         L.check(lib().uegan_input_transform(_p(pixels[b0:]), nb, h, w, oh, ow, _p(htab), hk, _p(vtab), vk, fl, _p(tmp), _p(out[b0:]), stream))
+    return out
+
+
+def input_transform_windows(images, windows, win, out_size, flips=None, out=None, stream=None):
+    """input_transform of crop windows that are read IN PLACE out of images resident on the device (uegan_input_transform_windows): images is a list
+    of uint8 [H_i, W_i, 3] device tensors -- sizes may differ, and a tensor may be a view with a row pitch (`big[:, 3:36]`): only its pixels have to
+    be contiguous; windows the list of (top, left), one per image; win the window's (h, w) or one int for both.  -> fp32 [B, 3, out_h, out_w], bit for
+    bit `input_transform(torch.stack([im[t:t + h, l:l + w] for ...]), out_size, flips)`.  A window that leaves its image is refused by the launcher
+    (RuntimeError) before anything of its call is launched."""
+    wh, ww = (win, win) if isinstance(win, int) else win
+    oh, ow = (out_size, out_size) if isinstance(out_size, int) else out_size
+    B = len(images)
+    if B < 1 or len(windows) != B or (flips is not None and len(flips) != B):
+        raise ValueError("input_transform_windows expects one (top, left) per image (and one flip code, if any), at least one image")
+    dev = images[0].device
+    for im in images:
+        if not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.device != dev or im.numel() == 0 or \
+                im.stride(2) != 1 or im.stride(1) != 3 or im.stride(0) % 3 or im.stride(0) < 3 * im.shape[1]:
+            raise ValueError("input_transform_windows expects uint8 [H, W, 3] tensors on one device whose pixels are contiguous (rows may have a pitch)")
+    if not L.is_emulated() and not dev.type == "cuda":
+        raise RuntimeError("uegan_amd ops need CUDA/HIP tensors (there is no CPU path)")
+    htab, hk = _device_table(ww, ow, dev)
+    vtab, vk = _device_table(wh, oh, dev)
+    if out is None:
+        out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=dev)
+    if stream is None and not L.is_emulated():
+        stream = torch.cuda.current_stream().cuda_stream
+    for b0 in range(0, B, MAX_IMAGES_PER_CALL):
+        nb = min(MAX_IMAGES_PER_CALL, B - b0)
+        tmp = torch.empty((nb, wh, ow, 3), dtype=torch.uint8, device=dev)
+        desc = (L.Window * nb)()
+        for i in range(nb):
+            im, (top, left) = images[b0 + i], windows[b0 + i]
+            desc[i] = L.Window(im.data_ptr(), im.stride(0) // 3, int(top), int(left), int(flips[b0 + i]) if flips is not None else 0, im.shape[0], im.shape[1])
+        L.check(lib().uegan_input_transform_windows(desc, nb, wh, ww, oh, ow, _p(htab), hk, _p(vtab), vk, _p(tmp), _p(out[b0:]), stream))
     return out
 
 
@@ -371,6 +409,93 @@ def get_input_decoder():
     return _input_decoder
 
 
+# where the decoded files live between their touches: "none" (nowhere: every touch decodes the file again) or "device" (the whole decoded image stays
+# in device memory from its first touch on, and a batch is cut out of the resident images by uegan_input_transform_windows: _ResidentStore)
+DATASET_CACHES = ("none", "device")
+DATASET_CACHE_DEFAULT_BYTES = 16 << 30      # per loader.  A setting, not a measurement: FiveK as the reference ships it decodes to about 11 GB
+_dataset_cache = "none"
+_dataset_cache_bytes = DATASET_CACHE_DEFAULT_BYTES
+
+
+def _cache_budget(gigabytes):
+    try:
+        ok = not isinstance(gigabytes, bool) and math.isfinite(float(gigabytes)) and float(gigabytes) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("dataset cache budget %r: expected a positive number of gigabytes" % (gigabytes,))
+    return int(float(gigabytes) * (1 << 30))
+
+
+def set_dataset_cache(name, gigabytes=None):
+    """the dataset cache of the loaders created from now on without a `cache` of their own: "none" (default) or "device", and the budget of "device"
+    per loader in GiB (default 16); returns the previous name"""
+    global _dataset_cache, _dataset_cache_bytes
+    if name not in DATASET_CACHES:
+        raise ValueError("unknown dataset cache %r (one of %s)" % (name, ", ".join(DATASET_CACHES)))
+    if gigabytes is not None and name != "device":
+        raise ValueError("a dataset cache budget (%r GiB) needs the dataset cache 'device'" % (gigabytes,))
+    budget = DATASET_CACHE_DEFAULT_BYTES if gigabytes is None else _cache_budget(gigabytes)
+    prev, _dataset_cache, _dataset_cache_bytes = _dataset_cache, name, budget
+    return prev
+
+
+def get_dataset_cache():
+    return _dataset_cache
+
+
+class _Entry:
+    """one resident image: `pixels` a uint8 [H, W, 3] view into a chunk of the store; `filled` once its decode or copy has been enqueued on the
+    loader's side stream, `pending` the pass (DeviceLoader.__iter__) whose earlier batch will do that"""
+    __slots__ = ("pixels", "filled", "pending")
+
+    def __init__(self, pixels):
+        self.pixels, self.filled, self.pending = pixels, False, -1
+
+
+class _ResidentStore:
+    """Decoded images kept in device memory, keyed by path: whole RGB images as uint8 [H][W][3], bump-allocated at 16-byte boundaries out of large
+    chunks.  No eviction: an epoch is a permutation, every file is used once per epoch, so a least-recently-used policy would evict each entry just
+    before its reuse; a static resident set hits for exactly its share of the files.  The first image that does not fit the budget is declined and so
+    is every later one.  The budget bounds the chunks' bytes; nothing is freed before close()."""
+    CHUNK_BYTES = 256 << 20
+
+    def __init__(self, budget, device, side):
+        self.budget, self.device, self.side = int(budget), device, side
+        self.chunks, self.cursor, self.reserved, self.used, self.full = [], 0, 0, 0, False
+        self.entries = {}
+
+    def _chunk(self, nbytes):
+        if self.side is None:
+            return torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.stream(self.side):      # the chunk belongs to the stream that writes and reads it
+            return torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+
+    def allocate(self, key, h, w):
+        """-> the new _Entry of an h x w image, or None: declined (from then on every allocation is)"""
+        n = (h * w * 3 + 15) // 16 * 16
+        if not self.full and (not self.chunks or self.cursor + n > self.chunks[-1].numel()):
+            room = self.budget - self.reserved
+            if n > room:
+                self.full = True
+            else:
+                self.chunks.append(self._chunk(max(n, min(self.CHUNK_BYTES, room))))
+                self.reserved += self.chunks[-1].numel()
+                self.cursor = 0
+        if self.full:
+            return None
+        entry = _Entry(self.chunks[-1][self.cursor:self.cursor + h * w * 3].view(h, w, 3))
+        self.cursor += n
+        self.used += n
+        self.entries[key] = entry
+        return entry
+
+    def close(self):
+        if self.chunks and self.side is not None:
+            torch.cuda.synchronize(self.device)      # a consumer may still read a NativeBatch view on its own stream
+        self.chunks, self.entries, self.full = [], {}, True
+
+
 def _read_file(path, size, dst, h, w):
     """worker of the device decoder: the file's bytes into the slot, its header parsed -> codecs.JpegInfo, or None for a file the device decoder
     declines (no JPEG, not baseline, ...: codecs.jpeg_info) or that changed since it was listed"""
@@ -408,7 +533,7 @@ class DeviceLoader:
                  file as a uint8 [1,h,w,3] device tensor (tester.enhance_native / run_test take them from there)"""
 
     def __init__(self, dataset, batch_size, img_size=512, resize_size=256, train=True, shuffle=True, drop_last=True, num_workers=8,
-                 device=None, prefetch=2, generator=None, shard=None, shard_seed=0, workers="thread", decode=None):
+                 device=None, prefetch=2, generator=None, shard=None, shard_seed=0, workers="thread", decode=None, cache=None, cache_bytes=None):
         """shard = (rank, world_size): this process iterates samples rank, rank + world, ... of the (shuffled) order -- one
         loader per GPU process.  The permutation of epoch e is then drawn from its own generator seeded
         shard_seed + e (the same on every rank, like DistributedSampler.set_epoch); crops and flips stay per-rank draws.
@@ -418,7 +543,21 @@ class DeviceLoader:
         spawned pool, the launching script needs its `if __name__ == "__main__":` guard).
         decode: "host" (Pillow in the workers), "device" (baseline JPEG files are decoded on the device from their bytes, bit-exact with Pillow, so the
         tensors are the same; every other file takes the Pillow route and is counted in `fallbacks`, per pass, and `fallbacks_total`), or None: what
-        set_input_decoder() chose.  "device" reads the files in threads."""
+        set_input_decoder() chose.  "device" reads the files in threads.
+        cache: "none" (every touch of a file decodes it again), "device", or None: what set_dataset_cache() chose.  "device" keeps the whole decoded
+        image of every file in device memory from its first touch on (_ResidentStore; cache_bytes: the budget in bytes, default 16 GiB or what
+        set_dataset_cache() set; no eviction: what does not fit is declined and decoded on every touch as with "none").  From the second touch on a
+        batch is made with no file access, no host decode and no host-to-device pixel copy: uegan_input_transform_windows reads the crop windows in
+        place.  The draws are consumed in the same order, so a seeded loader yields the tensors and names of cache="none", bit for bit.  The price:
+        a file that changes on disk after it was cached is served from the store until close().  In the native mode the NativeBatch tensors of
+        resident files are views into the store: read-only, alive as long as the loader.  Counters: cache_hits / cache_misses / cache_declined
+        (touches, since the loader was made), cache_entries, cache_bytes_used."""
+        self.cache = _dataset_cache if cache is None else cache
+        if self.cache not in DATASET_CACHES:
+            raise ValueError("unknown dataset cache %r (one of %s)" % (self.cache, ", ".join(DATASET_CACHES)))
+        if cache_bytes is not None and (self.cache != "device" or isinstance(cache_bytes, bool) or int(cache_bytes) != cache_bytes or cache_bytes < 0):
+            raise ValueError("cache_bytes=%r: expected a byte count, with cache='device'" % (cache_bytes,))
+        self.cache_hits = self.cache_misses = self.cache_declined = 0
         self.decode = _input_decoder if decode is None else decode
         if self.decode not in INPUT_DECODERS:
             raise ValueError("unknown input decoder %r (one of %s)" % (self.decode, ", ".join(INPUT_DECODERS)))
@@ -443,6 +582,18 @@ class DeviceLoader:
             self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=max(1, num_workers))
         self.side = None if self.emulated else torch.cuda.Stream(device=self.device)
         self.slots = [_Slot() for _ in range(self.prefetch + 1)]
+        self.store = None
+        if self.cache == "device":
+            self.store = _ResidentStore(_dataset_cache_bytes if cache_bytes is None else cache_bytes, self.device, self.side)
+        self._pass, self._file_sizes = 0, {}
+
+    @property
+    def cache_entries(self):
+        return len(self.store.entries) if self.store is not None else 0
+
+    @property
+    def cache_bytes_used(self):
+        return self.store.used if self.store is not None else 0
 
     def _n(self):
         n = len(self.dataset)
@@ -463,6 +614,8 @@ class DeviceLoader:
             if sl.copied is not None:
                 sl.copied.synchronize()
             sl.release()
+        if self.store is not None:
+            self.store.close()
 
     def __del__(self):
         try:
@@ -491,12 +644,14 @@ class DeviceLoader:
 
     # -- stage 1: host decode into the pinned buffer (threads) -------------------------------------------------------
     def _submit(self, slot, indices):
+        if self.store is not None:
+            return self._submit_cached(slot, indices)
         if self.decode == "device":
             return self._submit_files(slot, indices)
         return self._submit_pixels(slot, indices)
 
-    def _draw(self, slot, indices, align):
-        """the wait for the slot's earlier use, the items and the plan of a batch: per file (path, top, left, h, w, flip bits, offset of its pixels)"""
+    def _wait_slot(self, slot):
+        """the wait for the slot's earlier use"""
         for f in getattr(slot, "futures", None) or []:      # decodes left pending by an abandoned iterator still write into this slot
             try:
                 f.result()
@@ -506,6 +661,10 @@ class DeviceLoader:
         if slot.copied is not None:
             slot.copied.synchronize()            # the previous H2D copy out of this pinned buffer has finished
             slot.copied = None
+
+    def _draw(self, slot, indices, align):
+        """the wait for the slot's earlier use, the items and the plan of a batch: per file (path, top, left, h, w, flip bits, offset of its pixels)"""
+        self._wait_slot(slot)
         items = [self.dataset[i] for i in indices]
         plan, off = [], 0
         for a, b, name in items:
@@ -540,16 +699,130 @@ class DeviceLoader:
         slot.items, slot.plan, slot.nbytes, slot.out = items, plan, off, None
         slot.files, slot.pixel_bytes = files, pixel_bytes
 
+    def _submit_cached(self, slot, indices):
+        """cache="device": the draws of _draw in its order, and per file what the store says -- "hit" (resident, or made resident by an earlier batch
+        of this pass: uploads of a caching loader run in batch order), "miss" (a new entry: the WHOLE file is decoded, by the route of `decode`,
+        straight into the entry or through the slot) or "declined" (no room: today's route; with decode="host" in train mode that is the window
+        alone).  A hit takes nothing of the slot and starts no worker; the others get a 16-byte aligned pixel region and, with decode="device", a
+        region for the file's bytes behind all of them.  slot.plan holds the image's own (h, w); slot.how (kind, entry, region h, region w)."""
+        self._wait_slot(slot)
+        items = [self.dataset[i] for i in indices]
+        files_too = self.decode == "device"
+        plan, how, off = [], [], 0
+        for a, b, name in items:
+            for path in (a, b):
+                h, w = _image_size(path)
+                top, left, bits = draw_train_params(h, w, self.img_size, self.generator) if self.train else (0, 0, 0)
+                key = str(path)
+                entry = self.store.entries.get(key)
+                if entry is not None and (entry.filled or entry.pending == self._pass):
+                    kind, rh, rw = "hit", 0, 0
+                    self.cache_hits += 1
+                else:      # (an entry left unfilled by an abandoned pass is filled again)
+                    entry = entry if entry is not None else self.store.allocate(key, h, w)
+                    if entry is None:
+                        kind, (rh, rw) = "declined", (h, w) if files_too or not self.train else (self.img_size, self.img_size)
+                        self.cache_declined += 1
+                    else:
+                        kind, rh, rw, entry.pending = "miss", h, w, self._pass
+                        self.cache_misses += 1
+                off = (off + 15) // 16 * 16
+                plan.append((path, top, left, h, w, bits, off))
+                how.append((kind, entry, rh, rw))
+                off += rh * rw * 3
+        pixel_bytes = off = (off + 15) // 16 * 16
+        files = {}
+        if files_too:
+            for i, (path, *_) in enumerate(plan):
+                if how[i][0] != "hit":
+                    key = str(path)
+                    if key not in self._file_sizes:
+                        self._file_sizes[key] = os.path.getsize(path)
+                    files[i] = (off, self._file_sizes[key])
+                    off += (files[i][1] + 15) // 16 * 16
+        slot.ensure(max(off, 16), self.device, pinned=not self.emulated, shared=self.shared, mirror=files_too or not self.native)
+        host = slot.host.numpy()
+        slot.reads = {}
+        for i, ((path, top, left, h, w, _, o), (kind, _, rh, rw)) in enumerate(zip(plan, how)):
+            if kind == "hit":
+                continue
+            whole = kind == "miss" or not self.train
+            if files_too:
+                fo, size = files[i]
+                slot.reads[i] = self.pool.submit(_read_file, path, size, host[fo:fo + size], h, w)
+                slot.futures.append(slot.reads[i])
+            elif self.shared:
+                slot.futures.append(self.pool.submit(_worker_decode, slot.shm.name, o, str(path), top, left, rh, rw, whole))
+            else:
+                dst = host[o:o + rh * rw * 3].reshape(rh, rw, 3)
+                slot.futures.append(self.pool.submit(_decode_whole, path, dst) if whole else self.pool.submit(_decode_window, path, top, left, rh, rw, dst))
+        slot.items, slot.plan, slot.how, slot.nbytes, slot.out = items, plan, how, off, None
+        slot.files, slot.pixel_bytes = files, pixel_bytes
+
+    def _upload_cached(self, slot, stream_handle):
+        """cache="device", on the side stream: fill the entries of this batch's misses (decode="host": one copy out of the slot each; "device": the
+        files' bytes go up in one copy, uegan_jpeg_decode writes into the entry, a file it declines is decoded by Pillow here and copied), bring up
+        what was declined as today, then cut the batch out of the resident images -- one uegan_input_transform_windows call per 64 windows in train
+        mode, per run of equally sized images in test mode; the native mode hands out the images themselves.  A batch of hits is that call alone."""
+        from . import codecs
+        files_too = self.decode == "device"
+        if files_too and slot.nbytes > slot.pixel_bytes:
+            slot.dev[slot.pixel_bytes:slot.nbytes].copy_(slot.host[slot.pixel_bytes:slot.nbytes], non_blocking=True)
+        images, origins, transient = [], [], []
+        for i, ((path, top, left, h, w, _, o), (kind, entry, rh, rw)) in enumerate(zip(slot.plan, slot.how)):
+            if kind == "hit":
+                images.append(entry.pixels)
+                origins.append((top, left))
+                continue
+            n = rh * rw * 3
+            if files_too:
+                target = entry.pixels if kind == "miss" else torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
+                info, decoded = slot.reads[i].result(), False
+                if info is not None:
+                    try:
+                        fo, size = slot.files[i]
+                        codecs.jpeg_decode_into(info, slot.dev[fo:fo + size], target, stream=stream_handle)
+                        decoded = True
+                    except codecs.JpegDecodeError:
+                        pass
+                if not decoded:
+                    self.fallbacks += 1
+                    self.fallbacks_total += 1
+                    _decode_whole(path, slot.host.numpy()[o:o + n].reshape(h, w, 3))
+                    target.view(-1).copy_(slot.host[o:o + n], non_blocking=True)
+            elif kind == "miss" or self.native:      # (a declined native image is a buffer of its own: slot.dev would be overwritten by the next batch)
+                target = entry.pixels if kind == "miss" else torch.empty((h, w, 3), dtype=torch.uint8, device=self.device)
+                target.view(-1).copy_(slot.host[o:o + n], non_blocking=True)
+            else:
+                slot.dev[o:o + n].copy_(slot.host[o:o + n], non_blocking=True)
+                target = slot.dev[o:o + n].view(rh, rw, 3)
+                if self.train:
+                    top = left = 0                   # (the worker decoded the window alone)
+            if kind == "miss":
+                entry.filled = True
+            else:
+                transient.append(target)
+            images.append(target)
+            origins.append((top, left))
+        slot.transient = transient
+        if self.native:
+            return [im.view(1, im.shape[0], im.shape[1], 3) for im in images]
+        S = self.resize_size if self.train else self.img_size
+        out = torch.empty((len(images), 3, S, S), dtype=torch.float32, device=self.device)
+        if self.train:
+            input_transform_windows(images, origins, self.img_size, S, [p[5] for p in slot.plan], out=out, stream=stream_handle)
+            return out
+        i = 0
+        while i < len(images):
+            j = i + 1
+            while j < len(images) and images[j].shape == images[i].shape:
+                j += 1
+            input_transform_windows(images[i:j], origins[i:j], tuple(images[i].shape[:2]), S, None, out=out[i:j], stream=stream_handle)
+            i = j
+        return out
+
     def _submit_pixels(self, slot, indices):
-        for f in getattr(slot, "futures", None) or []:      # decodes left pending by an abandoned iterator still write into this slot
-            try:
-                f.result()
-            except Exception:
-                pass
-        slot.futures = []
-        if slot.copied is not None:
-            slot.copied.synchronize()            # the previous H2D copy out of this pinned buffer has finished
-            slot.copied = None
+        self._wait_slot(slot)
         items = [self.dataset[i] for i in indices]
         plan, off = [], 0
         for a, b, name in items:
@@ -624,6 +897,8 @@ class DeviceLoader:
         S = self.resize_size if self.train else self.img_size
 
         def run(stream_handle):
+            if self.store is not None:
+                return self._upload_cached(slot, stream_handle)
             if self.decode == "device":
                 pix = self._upload_files(slot, stream_handle)
                 if self.native:
@@ -666,6 +941,7 @@ class DeviceLoader:
 
     def __iter__(self):
         self.fallbacks = 0
+        self._pass += 1
         order = self._order()
         bs = self.batch_size
         batches = [order[i:i + bs] for i in range(0, len(order), bs)]
@@ -686,13 +962,22 @@ class DeviceLoader:
             for s in list(queue)[1:]:            # upload later batches whose decode has already finished
                 if s.out is None and all(f.done() for f in s.futures):
                     self._upload(s)
+                elif s.out is None and self.store is not None:
+                    break                        # a caching loader uploads in batch order: a later batch may hit what this one makes resident
             queue.popleft()
             out, names = head.out, [it[2] for it in head.items]
             if not self.emulated:
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(head.ready)
-                out.record_stream(cur)
+                for t in (head.transient if isinstance(out, list) else [out]):      # (views into the store are never freed before close())
+                    t.record_stream(cur)
             B = len(head.items)
+            if isinstance(out, list):            # cache="device", native: the resident images themselves, and buffers of their own for declined files
+                paths = [(str(it[0]), str(it[1])) for it in head.items]
+                head.out = None
+                free.append(head)
+                yield NativeBatch(out[0::2], out[1::2], names, paths)
+                continue
             if self.native:
                 imgs = [out[o:o + h * w * 3].view(1, h, w, 3) for _, _, _, h, w, _, o in head.plan]
                 paths = [(str(it[0]), str(it[1])) for it in head.items]
@@ -707,17 +992,18 @@ class DeviceLoader:
 
 
 def get_train_loader(root, img_size=512, resize_size=256, batch_size=8, shuffle=True, num_workers=8, drop_last=True, device=None, generator=None,
-                     shard=None, shard_seed=0, workers="thread", decode=None):
+                     shard=None, shard_seed=0, workers="thread", decode=None, cache=None, cache_bytes=None):
     """data_loader.py:72-90 with the transform on the device"""
     return DeviceLoader(ReferenceDataset(root), batch_size, img_size, resize_size, True, shuffle, drop_last, num_workers, device, generator=generator,
-                        shard=shard, shard_seed=shard_seed, workers=workers, decode=decode)
+                        shard=shard, shard_seed=shard_seed, workers=workers, decode=decode, cache=cache, cache_bytes=cache_bytes)
 
 
-def get_test_loader(root, img_size=512, batch_size=8, shuffle=False, num_workers=4, device=None, generator=None, workers="thread", decode=None):
+def get_test_loader(root, img_size=512, batch_size=8, shuffle=False, num_workers=4, device=None, generator=None, workers="thread", decode=None, cache=None,
+                    cache_bytes=None):
     """data_loader.py:93-110.  img_size=0: the native mode of DeviceLoader (NativeBatch: the decoded files as they are, for tester.run_test /
     tester.enhance_native to enhance at their own size)"""
     return DeviceLoader(ReferenceDataset(root), batch_size, img_size, img_size, False, shuffle, False, num_workers, device, generator=generator,
-                        workers=workers, decode=decode)
+                        workers=workers, decode=decode, cache=cache, cache_bytes=cache_bytes)
 
 
 class InputFetcher:

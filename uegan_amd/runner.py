@@ -20,6 +20,9 @@ What differs from the reference, on purpose:
   * UEGAN_IMAGE_FORMAT=jpeg (with UEGAN_JPEG_QUALITY=1..100, default 95) in the environment: those files are baseline JPEGs named .jpg, encoded on
     the device (tester.write_images); the metrics are computed before encoding and equal those of a PNG run.  UEGAN_JPEG_OPTIMIZE=1 with it:
     every file carries its own Huffman tables (smaller files, the same pixels after decoding).
+  * UEGAN_DATASET_CACHE=device (with UEGAN_DATASET_CACHE_GB=<GiB per loader>, default 16) in the environment: the train, validation and test
+    loaders keep every decoded file in device memory from its first touch on (data.set_dataset_cache); the same tensors.  validation.jsonl then
+    carries each validation's hits / misses / declined under "dataset_cache".
   * a step that prints nothing reads nothing from the device: the five losses are fetched (Trainer.loss_items) every --info_step only.
 """
 import json
@@ -142,10 +145,14 @@ def _append(path, record):
 def validate_epoch(args, G, loader, scorer, out_root, epoch, best):
     """trainer.py:213-286: enhance the validation set, write `validation_<epoch>/` and `validation_compare_<epoch>/`, score, track the best"""
     tag = "{:0>3.2f}".format(epoch)
+    before = (loader.cache_hits, loader.cache_misses, loader.cache_declined)
     res = tester.run_test(G, loader, save_dir=os.path.join(out_root, "validation_" + str(epoch)), tag=tag, metrics=args.is_test_psnr_ssim, nima=scorer,
                           suffix="valFakeExp", compare_dir=os.path.join(out_root, "validation_compare_" + str(epoch)),
                           compare_suffix="valRealRaw_valFakeExp")
     record = {"epoch": epoch, "images": len(res["names"])}
+    if loader.cache == "device":      # this validation's touches of the resident store: from the second validation on there are no misses
+        record["dataset_cache"] = {"hits": loader.cache_hits - before[0], "misses": loader.cache_misses - before[1],
+                                   "declined": loader.cache_declined - before[2]}
     if scorer is not None:
         record["nima"] = res["mean_nima"]
         best.update("nima", res["mean_nima"], epoch)
@@ -316,6 +323,33 @@ def _apply_input_decoder():
     data.set_input_decoder(name)
 
 
+DATASET_CACHE_ENV = "UEGAN_DATASET_CACHE"
+DATASET_CACHE_GB_ENV = "UEGAN_DATASET_CACHE_GB"
+
+
+def _apply_dataset_cache():
+    """UEGAN_DATASET_CACHE=none|device in the environment selects where the run's train, validation and test loaders keep the decoded files
+    (data.set_dataset_cache: "device" keeps every decoded image in device memory from its first touch on and cuts the batches out of the resident
+    images), UEGAN_DATASET_CACHE_GB=<positive number> the budget of "device" per loader in GiB (default 16); unset: the selection stays (default
+    "none").  Any other value is refused by name, and so is a budget without UEGAN_DATASET_CACHE=device.  They are not flags: the flag set is the
+    reference's."""
+    name, gb = os.environ.get(DATASET_CACHE_ENV), os.environ.get(DATASET_CACHE_GB_ENV)
+    if name is not None and name not in data.DATASET_CACHES:
+        raise ValueError("%s=%r: expected one of %s" % (DATASET_CACHE_ENV, name, ", ".join(data.DATASET_CACHES)))
+    budget = None
+    if gb is not None:
+        if name != "device":
+            raise ValueError("%s=%r needs %s=device" % (DATASET_CACHE_GB_ENV, gb, DATASET_CACHE_ENV))
+        try:
+            budget = float(gb)
+        except ValueError:
+            budget = None
+        if budget is None or not (budget > 0 and budget != float("inf")):
+            raise ValueError("%s=%r: expected a positive number" % (DATASET_CACHE_GB_ENV, gb))
+    if name is not None:
+        data.set_dataset_cache(name, budget)
+
+
 IMAGE_FORMAT_ENV = "UEGAN_IMAGE_FORMAT"
 JPEG_QUALITY_ENV = "UEGAN_JPEG_QUALITY"
 JPEG_OPTIMIZE_ENV = "UEGAN_JPEG_OPTIMIZE"
@@ -349,6 +383,7 @@ def main(argv=None):
     _apply_png_encoder()
     _apply_image_format()
     _apply_input_decoder()
+    _apply_dataset_cache()
     args = argv if hasattr(argv, "mode") else config.get_config(argv)
     if args.mode not in ("train", "test"):
         raise NotImplementedError("Mode [{}] is not found".format(args.mode))                                          # main.py:50
